@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec of ResNet-18 (ImageNet, ls-1 weights / ls-2 activations) eval forward.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
+A plain run times exactly K steps after W warm-up steps and prints the headline figure; --full adds everything else the
+line can carry (one-stream region, per-kernel roofline, all-gather alone, parity probe, cpu_baseline, other configs).
 One process per GPU; each rank holds a full replica, takes its own 256 synthetic 3x224x224 images per step (weak
 scaling) and the ranks all-gather their logits over RCCL every step.  Rank 0 prints ONE JSON line (see DESIGN.md
 "Measurement").  Under torchrun the ranks are torchrun's (RANK / LOCAL_RANK / WORLD_SIZE in the environment); started
@@ -319,6 +321,24 @@ def cpu_baseline(arch, model, sample):
                       f'(the faster of 16 / 32), host cpu_count={os.cpu_count()}'}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32; an array above DUMP_MAX_BYTES (all of them together)
+    is cut to a fixed, seeded sample of its rows, the same for every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            row = a[0].nbytes if a.ndim > 1 else a.itemsize
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, budget // row), replace=False))
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 class _Clock:
     """Stream events on the GPU, host clock in the CPU plumbing mode (--device cpu: the gloo / launcher test)."""
 
@@ -378,8 +398,14 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--min-seconds', type=float, default=5.0,
-                    help='repeat the bracket of --steps timed steps until this much time has been timed (headline region)')
+    ap.add_argument('--min-seconds', type=float, default=None,
+                    help='repeat the bracket of --steps timed steps until this much time has been timed (headline region; '
+                         'default: one bracket, exactly --steps timed steps)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the one-stream region, the per-kernel roofline, '
+                         'the all-gather alone, the parity probe, cpu_baseline and the other configurations')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the logits of the last timed step to DIR/logits.npy (float32)')
     ap.add_argument('--batch', type=int, default=256, help='images per GPU per step')
     ap.add_argument('--cpu-sample', type=int, default=64,
                     help='batch of the cpu_baseline leg (0 = skip); 64 = the bounded sample SURVEY 8(d) names (B = 64)')
@@ -451,7 +477,7 @@ def main():
     x = torch.randn(args.batch, 3, args.image_size, args.image_size, generator=g).to(device)       # resident in HBM before timing
     gathered = torch.empty((world * args.batch, 1000), dtype=torch.float32, device=device) if dist.is_initialized() else None
     in_group = dist.is_initialized()
-    roofline = cuda and not args.no_roofline
+    roofline = cuda and args.full and not args.no_roofline
     nstreams = args.streams if cuda else 1
     PATH_KERNELS = ('lsq_act_quant', 'lsq_xnor_conv2d', 'lsq_signw_conv2d')
 
@@ -483,12 +509,14 @@ def main():
     # is queued on one of `nstreams` HIP streams (round robin) while the logits of step i - 1 are all-gathered on the main
     # stream behind that forward's event.  nstreams = 1: everything on the one stream, every kernel alone on the chip.
     pipe = StreamPipeline(lambda shard: local_forward(model, shard), device, nstreams)
+    last = [None]                                          # the logits of the last step consumed (--dump-outputs)
 
     def run_steps(n):
         window = []
 
         def consume():
             y = window.pop(0).result()
+            last[0] = y
             if in_group:
                 all_gather_logits(y, gathered, always_collective=True)
 
@@ -502,15 +530,19 @@ def main():
     with torch.no_grad():
         run_steps(max(args.warmup, 2 * nstreams))
         sync()
-        elapsed, reps, rep_ms = bracket(run_steps, args.min_seconds)
+        elapsed, reps, rep_ms = bracket(run_steps, args.min_seconds or 0.0)
     steps_timed = reps * args.steps
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: this rank's logits, or all ranks' after the all-gather
+        dump_outputs(args.dump_outputs, {'logits': gathered if in_group else last[0]})
 
-    # ---- one stream: the reference point of rounds 1-4 and the region the per-kernel figures come from (each kernel alone on
+    # ---- --full only from here to the line: what the headline figure does not need.
+    # one stream: the reference point of rounds 1-4 and the region the per-kernel figures come from (each kernel alone on
     # the chip, as in the rocprofv3 summaries under profiles/).  HIP events sit around the launches of the two path kernels in
     # the first step of every group of steps only (an event pair costs a few microseconds of stream time).
     single = None
     table, by_shape, timed_table = {}, {}, {}
-    if nstreams > 1 or roofline or world > 1:            # (N > 1: the line always carries the one-stream figure beside the pipelined one)
+    if args.full and (nstreams > 1 or roofline or world > 1):   # (N > 1: the --full line carries the one-stream figure beside the pipelined one)
         one = StreamPipeline(lambda shard: local_forward(model, shard), device, 1)
 
         def run_single(n, sample_every=0):
@@ -539,7 +571,7 @@ def main():
             # every kSampleEvery-th step carries them -- a fixed rate, whatever --steps is (round 5 tied it to --steps / 10: under
             # the driver's --steps 20 every second step of the timed region carried 32 event pairs)
             _hip.pause_timing(True)
-            s_elapsed, s_reps, s_rep_ms = bracket(lambda n: run_single(n, 0), min(args.min_seconds, 2.0))
+            s_elapsed, s_reps, s_rep_ms = bracket(lambda n: run_single(n, 0), min(2.0 if args.min_seconds is None else args.min_seconds, 2.0))
             _hip.pause_timing(False)
             if roofline:
                 kSampleEvery, kSampleSteps = 20, 100
@@ -552,7 +584,7 @@ def main():
                   'ms_per_step_best_repetition': min(s_rep_ms)}
 
     allgather = None
-    if in_group:
+    if in_group and args.full:
         # the exchange step alone: [batch, 1000] fp32 logits per rank, events on the launch stream
         logits = torch.randn(args.batch, 1000, device=device)
         for _ in range(5):
@@ -599,7 +631,7 @@ def main():
             out['pipelined'] = {'streams': nstreams, 'value': value, 'ms_per_step': out['ms_per_step'],
                                 'vs_single_stream': value / single['value'] if single else None}
         out['value_definition'] = ('whole-job images/s of the headline region: consecutive steps on %d HIP stream(s), the product\'s evaluate '
-                                   'path (rounds 1-4 reported the one-stream step: `single_stream`, timed on the same footing -- '
+                                   'path (rounds 1-4 reported the one-stream step: `single_stream` under --full, timed on the same footing -- '
                                    'uninstrumented bracket of --steps steps, barrier + synchronize on both sides)' % nstreams)
         if single is not None:
             out['single_stream'] = single
@@ -649,14 +681,14 @@ def main():
             detail['by_layer_shape'] = shapes
         if allgather is not None:
             out['allgather'] = allgather
-        if cuda and world == 1:
+        if args.full and cuda and world == 1:
             try:
                 out['parity'] = parity_probe(device)
             except Exception as exc:                                       # (the numbers above stand without it; say what happened)
                 out['parity'] = {'error': repr(exc)[:200]}
-        if cuda and args.cpu_sample > 0 and world == 1:
+        if args.full and cuda and args.cpu_sample > 0 and world == 1:
             out['cpu_baseline'] = cpu_baseline(arch, model, args.cpu_sample)
-        if cuda and world == 1 and not args.no_configs and args.act == 'ls-2':
+        if args.full and cuda and world == 1 and not args.no_configs and args.act == 'ls-2':
             # the other single-GPU configurations BASELINE.json lists, as short legs of this process (one stream, eager)
             cfg = {}
             # the north_star-literal __popcll XNOR kernel on the headline network, beside the int8-MFMA one above

@@ -7,17 +7,17 @@
 cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 tag=${1:-r03}; o=gpurun_out
 mkdir -p $o
-python bench.py --detail $o/${tag}_bench_n1_ls2_detail.json > $o/${tag}_bench_n1_ls2.json 2> $o/bench_ls2.err
-python bench.py --act fp --no-configs --detail $o/${tag}_bench_n1_fpact_detail.json > $o/${tag}_bench_n1_fpact.json 2> $o/bench_fp.err
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 \
+python bench.py --full --detail $o/${tag}_bench_n1_ls2_detail.json > $o/${tag}_bench_n1_ls2.json 2> $o/bench_ls2.err
+python bench.py --full --act fp --no-configs --detail $o/${tag}_bench_n1_fpact_detail.json > $o/${tag}_bench_n1_fpact.json 2> $o/bench_fp.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 \
   --steps 100 --cpu-sample 0 --no-configs > $o/${tag}_bench_torchrun_n1_ls2.json 2> $o/bench_torchrun.err
 rm -rf $o/prof_final
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_final -- python bench.py --steps 30 --warmup 5 --min-seconds 0 --cpu-sample 0 --no-configs --streams 1 > $o/prof_final.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_final -- python bench.py --full --steps 30 --warmup 5 --min-seconds 0 --cpu-sample 0 --no-configs --streams 1 > $o/prof_final.log 2>&1
 f=$(ls -t $o/prof_final/*/*kernel_trace.csv | head -1)
 python scripts/trace_summary.py $f 10 > $o/${tag}_rocprofv3_per_step_summary.csv
 cp $(ls -t $o/prof_final/*/*kernel_stats.csv | head -1) $o/${tag}_rocprofv3_kernel_stats_incl_warmup.csv
 rm -rf $o/prof_fp
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_fp -- python bench.py --act fp --steps 30 --warmup 5 --min-seconds 0 --cpu-sample 0 --no-configs --streams 1 > $o/prof_fp.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_fp -- python bench.py --full --act fp --steps 30 --warmup 5 --min-seconds 0 --cpu-sample 0 --no-configs --streams 1 > $o/prof_fp.log 2>&1
 python scripts/trace_summary.py $(ls -t $o/prof_fp/*/*kernel_trace.csv | head -1) 10 > $o/${tag}_rocprofv3_per_step_summary_fpact.csv
 scripts/pmc_traffic.sh $o/${tag}_pmc_hbm_traffic.json > $o/pmc.log 2>&1
 scripts/pmc_traffic.sh $o/${tag}_pmc_hbm_traffic_fpact.json --act fp > $o/pmc_fp.log 2>&1
@@ -42,7 +42,7 @@ python scripts/kbench.py --fold > $o/${tag}_kbench_bnfold.txt 2>&1
 python scripts/kbench.py --evict 600 --retouch > $o/${tag}_kbench_cold.txt 2>&1
 # round 5: what runs under what when consecutive steps alternate between two HIP streams (the headline's issue order)
 rm -rf $o/prof_ov
-rocprofv3 --kernel-trace --output-format csv -d $o/prof_ov -- python bench.py --steps 30 --warmup 5 --min-seconds 0 --cpu-sample 0 --no-configs --no-roofline --streams 2 > $o/prof_ov.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $o/prof_ov -- python bench.py --full --steps 30 --warmup 5 --min-seconds 0 --cpu-sample 0 --no-configs --no-roofline --streams 2 > $o/prof_ov.log 2>&1
 python scripts/overlap_trace.py $(ls -t $o/prof_ov/*/*kernel_trace.csv | head -1) 10 110 > $o/${tag}_two_stream_overlap.txt 2>&1
 python scripts/queue_gaps.py $(ls -t $o/prof_ov/*/*kernel_trace.csv | head -1) 150 0 > $o/${tag}_queue_gaps.txt 2>&1
 rm -rf $o/prof_ov

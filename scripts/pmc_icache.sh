@@ -9,7 +9,7 @@ rm -rf $dir; mkdir -p $dir
 p=0
 for c in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU"; do
   p=$((p+1))
-  timeout -k 5 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $dir/net$p -- python bench.py --steps 3 --warmup 2 --min-seconds 0 --cpu-sample 0 --no-configs --no-roofline --streams 1 > $dir/net$p.log 2>&1
+  timeout -k 5 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $dir/net$p -- python bench.py --full --steps 3 --warmup 2 --min-seconds 0 --cpu-sample 0 --no-configs --no-roofline --streams 1 > $dir/net$p.log 2>&1
 done
 python - "$dir" > $out <<'PY'
 import collections, csv, glob, sys

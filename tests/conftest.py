@@ -28,26 +28,39 @@ def pytest_collection_modifyitems(config, items):
             item.add_marker(skip)
 
 
+def golden_parts(name):
+    """tests/golden/<name>.npz and its continuation files <name>.1.npz, <name>.2.npz, ... (make_fixtures.py splits a
+    fixture so that no file exceeds 1 MiB)."""
+    parts, i = [os.path.join(GOLDEN, name + '.npz')], 1
+    while os.path.exists(os.path.join(GOLDEN, f'{name}.{i}.npz')):
+        parts.append(os.path.join(GOLDEN, f'{name}.{i}.npz'))
+        i += 1
+    return parts
+
+
 class Golden:
     """Lazy access to tests/golden/*.npz as torch tensors."""
 
     def __init__(self, name):
-        self._z = np.load(os.path.join(GOLDEN, name + '.npz'))
+        self._z = {}
+        for path in golden_parts(name):
+            z = np.load(path)
+            self._z.update((k, z) for k in z.files)
 
     def __contains__(self, key):
-        return key in self._z.files
+        return key in self._z
 
     def keys(self):
-        return list(self._z.files)
+        return list(self._z)
 
     def np(self, key):
-        return self._z[key]
+        return self._z[key][key]
 
     def __getitem__(self, key):
-        return torch.from_numpy(np.array(self._z[key]))
+        return torch.from_numpy(np.array(self.np(key)))
 
     def text(self, key):
-        return bytes(self._z[key]).decode()
+        return bytes(self.np(key)).decode()
 
     def json(self, key):
         return json.loads(self.text(key))

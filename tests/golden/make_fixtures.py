@@ -36,15 +36,30 @@ assert os.path.realpath(r_q.__file__).startswith(os.path.realpath(REF)), r_q.__f
 torch.set_num_threads(8)
 
 
+MAX_FILE_BYTES = 900 * 1024       # committed files stay under 1 MiB: a larger fixture continues in <name>.1.npz, <name>.2.npz, ...
+
+
 def save(name, **arrays):
     out = {}
     for k, v in arrays.items():
         if isinstance(v, torch.Tensor):
             v = v.detach().cpu().numpy()
         out[k] = v
-    path = os.path.join(HERE, name + '.npz')
-    np.savez_compressed(path, **out)
-    print(f'{name}.npz  {os.path.getsize(path) / 1024:.1f} KiB')
+    parts, part = [], {}
+    for k, v in out.items():
+        if part and sum(a.nbytes for a in part.values()) + v.nbytes > MAX_FILE_BYTES:   # (uncompressed bytes: a safe bound)
+            parts.append(part)
+            part = {}
+        part[k] = v
+    parts.append(part)
+    i = 1
+    while os.path.exists(os.path.join(HERE, f'{name}.{i}.npz')):          # continuation files of an earlier, larger run
+        os.remove(os.path.join(HERE, f'{name}.{i}.npz'))
+        i += 1
+    for i, part in enumerate(parts):
+        path = os.path.join(HERE, name + ('.npz' if i == 0 else f'.{i}.npz'))
+        np.savez_compressed(path, **part)
+        print(f'{os.path.basename(path)}  {os.path.getsize(path) / 1024:.1f} KiB')
 
 
 def packbits(t):

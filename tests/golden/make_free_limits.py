@@ -49,8 +49,13 @@ NETS = {'imagenet_ls1w_ls2a': (2, 3, 64, 64), 'imagenet_ls1w_lsTa': (2, 3, 64, 6
 
 
 def load(name):
-    z = np.load(os.path.join(HERE, name + '.npz'))
-    return {k: torch.from_numpy(np.array(z[k])) for k in z.files}
+    out, i, path = {}, 0, os.path.join(HERE, name + '.npz')
+    while os.path.exists(path):                       # <name>.npz, then its continuation files <name>.1.npz, ...
+        z = np.load(path)
+        out.update((k, torch.from_numpy(np.array(z[k]))) for k in z.files)
+        i += 1
+        path = os.path.join(HERE, f'{name}.{i}.npz')
+    return out
 
 
 def rel_err(y, ref):

@@ -9,6 +9,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,11 +62,14 @@ def _one_json_line(stdout):
     return json.loads(lines[0])
 
 
-def test_bench_starts_its_own_ranks():
+def test_bench_starts_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher around it: two ranks, gloo in the CPU plumbing mode, ONE JSON line."""
-    r = subprocess.run([sys.executable, BENCH, '--gpus', '2'] + SMALL, env=_env(), capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--full', '--dump-outputs', str(tmp_path)] + SMALL, env=_env(),
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = _one_json_line(r.stdout)
+    logits = np.load(tmp_path / 'logits.npy')                     # rank 0 writes what the all-gather handed every rank
+    assert logits.shape == (4, 1000) and logits.dtype == np.float32 and np.isfinite(logits).all()
     assert out['n_gpus'] == 2 and out['launcher'] == {'kind': 'self', 'ranks': 2, 'numa_pinning_rank0': None}
     assert out['config']['global_batch'] == 4 and out['scaling'] == 'weak' and out['steps'] == 2
     assert out['allgather']['world_size_seen_by_backend'] == 2 and out['allgather']['bytes_received_per_rank'] == 2 * 1000 * 4
@@ -94,6 +98,28 @@ def test_single_rank_needs_no_process_group():
     assert r.returncode == 0, r.stderr[-2000:]
     out = _one_json_line(r.stdout)
     assert out['n_gpus'] == 1 and out['launcher']['kind'] == 'none' and 'allgather' not in out
+
+
+def test_plain_run_times_exactly_steps_and_dumps_the_same_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, carries the headline keys and none of the --full legs; with the
+    same arguments two runs write the same logits of their last timed step."""
+    args = [sys.executable, BENCH, '--gpus', '1', '--device', 'cpu', '--batch', '2', '--image-size', '32', '--steps', '3',
+            '--warmup', '1']
+    dumps = []
+    for run in ('a', 'b'):
+        r = subprocess.run(args + ['--dump-outputs', str(tmp_path / run)], env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = _one_json_line(r.stdout)
+        assert out['steps'] == 3 and out['steps_timed'] == 3 and out['repetitions'] == 1
+        assert out['ms_per_step'] > 0 and abs(out['ms_per_step'] - 1e3 * out['timed_seconds'] / 3) < 1e-9
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype'):
+            assert k in out, k
+        for k in ('single_stream', 'roofline', 'allgather', 'parity', 'cpu_baseline', 'configs'):
+            assert k not in out, k
+        assert sorted(os.listdir(tmp_path / run)) == ['logits.npy']
+        dumps.append(np.load(tmp_path / run / 'logits.npy'))
+    assert dumps[0].shape == (2, 1000) and dumps[0].dtype == np.float32 and np.isfinite(dumps[0]).all()
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 @pytest.mark.gpu

@@ -257,7 +257,7 @@ def test_sharded_step_on_two_streams_over_rccl_with_one_rank():
             dist.destroy_process_group()
 
 
-def test_bench_line_under_torchrun_with_one_rank():
+def test_bench_line_under_torchrun_with_one_rank(tmp_path):
     """The driver's launch line with one rank: rank 0's ONE JSON line carries the two-stream headline, the one-stream region,
     both path kernels under fixed roofline keys, the all-gather and the parity object."""
     import json
@@ -268,7 +268,7 @@ def test_bench_line_under_torchrun_with_one_rank():
     from quant.common.rank_launcher import free_port
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(free_port()), os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '10', '--warmup', '3',
-           '--min-seconds', '0', '--cpu-sample', '0', '--no-configs']
+           '--min-seconds', '0', '--cpu-sample', '0', '--no-configs', '--full', '--dump-outputs', str(tmp_path)]
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -282,3 +282,6 @@ def test_bench_line_under_torchrun_with_one_rank():
         assert 0 < out['roofline'][k]['frac'] < 1
     assert out['allgather']['backend'] == 'nccl' and out['allgather']['world_size_seen_by_backend'] == 1
     assert len(lines[0]) < 8000                                   # (the driver keeps short lines whole)
+    import numpy as np
+    logits = np.load(tmp_path / 'logits.npy')                     # the last timed step's all-gathered logits
+    assert logits.shape == (256, 1000) and logits.dtype == np.float32 and np.isfinite(logits).all()
