@@ -645,6 +645,69 @@ def ste_backward(x: torch.Tensor, grad_q: torch.Tensor, scales: Optional[torch.T
     return out
 
 
+# ---- the training library (include/lsq_hip_train.h): a second shared object, loaded on first use
+_TRAIN_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib', 'liblsq_hip_train.so')
+TRAIN_ABI_VERSION = 1
+_train_lib = None
+
+
+def train_library_path() -> str:
+    return _TRAIN_LIB_PATH
+
+
+def train_lib():
+    """Load (once) and return the training library; raises if it has not been built (no fallback, as ``lib()``)."""
+    global _train_lib
+    if _train_lib is None:
+        with _lock:
+            if _train_lib is None:
+                if not os.path.exists(_TRAIN_LIB_PATH):
+                    raise LsqHipError(
+                        f'{_TRAIN_LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
+                        '(or `make -C ml-quant_amd/csrc/train`). The HIP path has no fallback.')
+                handle = ctypes.CDLL(_TRAIN_LIB_PATH)
+                vp, i32, gp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ConvGeom)
+                handle.lsq_train_abi_version.restype = i32
+                handle.lsq_train_abi_version.argtypes = []
+                handle.lsq_train_wgrad_workspace_bytes.restype = ctypes.c_size_t
+                handle.lsq_train_wgrad_workspace_bytes.argtypes = [gp, i32]
+                handle.lsq_train_wgrad.restype = i32
+                handle.lsq_train_wgrad.argtypes = [vp, i32, vp, vp, gp, vp, vp, ctypes.c_size_t, vp]
+                if handle.lsq_train_abi_version() != TRAIN_ABI_VERSION:
+                    raise LsqHipError('liblsq_hip_train.so ABI version mismatch')
+                _train_lib = handle
+    return _train_lib
+
+
+_wgrad_ws_cache = {}
+
+
+def wgrad(planes: torch.Tensor, kx: int, xscales: torch.Tensor, gy: torch.Tensor, geom: ConvGeom) -> torch.Tensor:
+    """grad_wq [O, C, KH, KW] = conv2d_weight(x_q, grad_y) with x_q = sum_p xscales[p][n] (2 bit_p - 1) read from the
+    activation planes ``planes`` (lsq_train_wgrad), on the current stream.  The split-K slabs live in a workspace cached
+    per (device, stream) like the solver's (any content; kernels of one stream run in order)."""
+    gy, xscales = _f32c(gy), _f32c(xscales)
+    if planes.dtype != torch.int64 or not planes.is_contiguous():
+        raise TypeError('activation planes are a contiguous int64 tensor')
+    tl = train_lib()
+    need = int(tl.lsq_train_wgrad_workspace_bytes(ctypes.byref(geom), int(kx)))
+    ws = None
+    if need:
+        key = (gy.device.index, stream_ptr(gy.device))
+        ws = _wgrad_ws_cache.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty((need,), dtype=torch.uint8, device=gy.device)
+            _remember(_wgrad_ws_cache, key, ws)
+    out = torch.empty((geom.O, geom.C, geom.KH, geom.KW), dtype=torch.float32, device=gy.device)
+    ho, wo = out_hw(geom)
+    with _on(gy), _Timed('lsq_train_wgrad', 4 * gy.numel() + 8 * kx * act_plane_words(geom) + 4 * out.numel(),
+                         2 * geom.N * ho * wo * geom.O * geom.C * geom.KH * geom.KW):
+        check(tl.lsq_train_wgrad(planes.data_ptr(), int(kx), xscales.data_ptr(), gy.data_ptr(), ctypes.byref(geom),
+                                 out.data_ptr(), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(gy.device)),
+              'lsq_train_wgrad')
+    return out
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

@@ -8,15 +8,20 @@ and ``F.conv2d``.  Here the same step is one ``torch.autograd.Function`` around 
 forward   the weight scales are computed and cached (``copy_`` into the ``v1..vk`` buffers, as the reference does);
           ``lsq_act_quant`` solves the per-sample activation scales and packs the sign planes; ``lsq_pack_weight`` +
           ``lsq_xnor_conv2d`` (binary activations) or ``lsq_signw_conv2d`` (fp activations) produce the output -- the
-          kernels of the inference path.  Saved for backward: the input, both sets of scales.
+          kernels of the inference path.  Saved for backward: the input, both sets of scales and, for binary activations,
+          this step's sign planes (a buffer of the step, not the module's: a second forward of the same module before
+          backward must not change what backward reads).
 backward  grad_bias = sum of grad_y;
           grad_xq   = conv_transpose2d(grad_y, w_q): one ``lsq_signw_conv2d`` per weight plane over the flipped,
                       transposed sign weights (packed once per step), the plane's per-output-channel scale folded into
                       its input-channel pre-scale, later planes accumulated through the residual epilogue; stride 2 by
                       zero insertion;
           grad_x    = ``lsq_ste_backward``: straight-through estimator of every sign of the quantizer chain + clamp mask;
-          grad_wq   = correlation of x_q (``lsq_quant_values``: the quantizer's value from the saved input and scales) with
-                      grad_y -- ``torch.nn.grad.conv2d_weight`` (MIOpen), the one piece without a kernel of its own;
+          grad_wq   = correlation of x_q with grad_y: binary activations -- ``lsq_train_wgrad`` (liblsq_hip_train.so) reads
+                      x_q = sum_p v_p[n] (2 bit_p - 1) from the saved sign planes and scales, a bf16 matrix-core GEMM with
+                      exact +-1 signs and a three-term split of v_p grad_y; fp activations -- the clamp's
+                      value (``lsq_quant_values``) and ``torch.nn.grad.conv2d_weight`` (MIOpen).  The kernel is taken when
+                      ``WGRAD_KERNEL`` is True; by default (False) binary activations go the second way too;
           grad_w    = ``lsq_ste_backward`` over the weight rows.
 Geometries the transposed convolution does not take (groups, dilation, strides other than 1 / 2) fall back to the torch
 formulation of the module; results are those of the reference's graph within fp32 reassociation (tests: f9_train).
@@ -27,6 +32,11 @@ from typing import List, Optional
 import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
+
+# binary activations: the weight gradient on lsq_train_wgrad (True) or on lsq_quant_values + conv2d_weight (False).  Off by
+# default: the batch-256 ResNet-18 train step measured slower with the kernel than with MIOpen (DESIGN 4.7,
+# profiles/train_step.json) -- the kernel stays the default only once it makes the step faster.
+WGRAD_KERNEL = False
 
 
 def supported(conv, x: torch.Tensor) -> bool:
@@ -100,7 +110,10 @@ class _QuantConv2dStep(torch.autograd.Function):
             # once, the kernels rewrite the interior); the scales are saved for backward and stay a tensor of this step
             key = ('train_planes', geom.key()[:4], geom.pad_h, geom.pad_w, k, x.device, _hip.stream_ptr(x.device))
             planes = conv._hip_cache.get(key)
-            if planes is None:
+            if WGRAD_KERNEL and ctx.needs_input_grad[1]:
+                # backward reads these planes: a buffer of this step (zero halo), saved with it
+                planes = torch.zeros((k * _hip.act_plane_words(geom),), dtype=torch.int64, device=x.device)
+            elif planes is None:
                 planes = torch.zeros((k * _hip.act_plane_words(geom),), dtype=torch.int64, device=x.device)
                 stale = [kk for kk in list(conv._hip_cache) if isinstance(kk, tuple) and kk[0] == 'train_planes']
                 for kk in stale[:max(0, len(stale) - 3)]:
@@ -123,7 +136,9 @@ class _QuantConv2dStep(torch.autograd.Function):
             conv.last_act_scales = xscales
         ctx.conv, ctx.geom, ctx.alpha = conv, geom, alpha
         ctx.has_bias = bias is not None
-        ctx.save_for_backward(x, weight, wscales, xscales if xscales is not None else x.new_empty(0))
+        step_planes = planes if (xscales is not None and WGRAD_KERNEL and ctx.needs_input_grad[1]) else None
+        ctx.save_for_backward(x, weight, wscales, xscales if xscales is not None else x.new_empty(0),
+                              step_planes if step_planes is not None else x.new_empty(0, dtype=torch.int64))
         return y
 
     @staticmethod
@@ -131,7 +146,7 @@ class _QuantConv2dStep(torch.autograd.Function):
     def backward(ctx, gy):
         from quant import _hip
         conv, geom, alpha = ctx.conv, ctx.geom, ctx.alpha
-        x, weight, wscales, xscales = ctx.saved_tensors
+        x, weight, wscales, xscales, planes = ctx.saved_tensors
         xscales = xscales if xscales.numel() else None
         gy = gy.contiguous()
         n, c, h, w = x.shape
@@ -163,8 +178,11 @@ class _QuantConv2dStep(torch.autograd.Function):
                 gxq = out
             gx = _hip.ste_backward(x, gxq, xscales, alpha)
         if need_w:
-            xq = _hip.quant_values(x, xscales, alpha)
-            gwq = torch.nn.grad.conv2d_weight(xq, weight.shape, gy, conv.stride, conv.padding, conv.dilation, 1)
+            if planes.numel():
+                gwq = _hip.wgrad(planes, xscales.shape[0], xscales, gy, geom)
+            else:
+                xq = _hip.quant_values(x, xscales, alpha)
+                gwq = torch.nn.grad.conv2d_weight(xq, weight.shape, gy, conv.stride, conv.padding, conv.dilation, 1)
             gw = _hip.ste_backward(weight.detach(), gwq, wscales, -1.0)
         return gx, gw, gb, None
 
