@@ -708,6 +708,75 @@ def wgrad(planes: torch.Tensor, kx: int, xscales: torch.Tensor, gy: torch.Tensor
     return out
 
 
+# ---- the linear-layer library (include/lsq_hip_linear.h): a third shared object, loaded on first use
+_LINEAR_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib', 'liblsq_hip_linear.so')
+LINEAR_ABI_VERSION = 1
+LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
+LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
+_linear_lib = None
+
+
+def linear_library_path() -> str:
+    return _LINEAR_LIB_PATH
+
+
+def linear_lib():
+    """Load (once) and return the linear-layer library; raises if it has not been built (no fallback, as ``lib()``)."""
+    global _linear_lib
+    if _linear_lib is None:
+        with _lock:
+            if _linear_lib is None:
+                if not os.path.exists(_LINEAR_LIB_PATH):
+                    raise LsqHipError(
+                        f'{_LINEAR_LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
+                        '(or `make -C ml-quant_amd/csrc/linear`). The HIP path has no fallback.')
+                handle = ctypes.CDLL(_LINEAR_LIB_PATH)
+                vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+                handle.lsq_linear_abi_version.restype = i32
+                handle.lsq_linear_abi_version.argtypes = []
+                handle.lsq_linear_xnor.restype = i32
+                handle.lsq_linear_xnor.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, i64, i64, i64, vp, vp]
+                if handle.lsq_linear_abi_version() != LINEAR_ABI_VERSION:
+                    raise LsqHipError('liblsq_hip_linear.so ABI version mismatch')
+                _linear_lib = handle
+    return _linear_lib
+
+
+def linear_xnor(planes: torch.Tensor, kx: int, xscales: torch.Tensor, rows_per_scale: int, wbits: torch.Tensor,
+                wsum: torch.Tensor, wscales: torch.Tensor, bias: Optional[torch.Tensor], M: int, F: int, O: int) -> torch.Tensor:
+    """y [M, O] = F.linear(x_q, w_q, bias) from sign planes (lsq_linear_xnor): ``planes`` / ``xscales`` [kx, M / rows_per_scale]
+    are what lsq_act_quant wrote for (N, rows_per_scale * F, 1, 1), ``wbits`` / ``wsum`` / ``wscales`` [kw, O] what
+    lsq_pack_weight took and wrote for (O, F, 1, 1).  Bit for bit the 1x1 lsq_xnor_conv2d over (M, F, 1, 1)."""
+    if planes.dtype != torch.int64 or wbits.dtype != torch.int64 or wsum.dtype != torch.int32:
+        raise TypeError('planes and wbits are int64 tensors, wsum an int32 tensor')
+    xscales, wscales = _f32c(xscales), _f32c(wscales)
+    if bias is not None:
+        bias = _f32c(bias)
+    tensors = [planes, xscales, wbits, wsum, wscales] + ([] if bias is None else [bias])
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError('lsq_linear_xnor: operands must be contiguous')
+    dev = planes.device
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError('lsq_linear_xnor: every operand on the same cuda device')
+    M, F, O, kx, t = int(M), int(F), int(O), int(kx), int(rows_per_scale)
+    if min(M, F, O, kx, t) <= 0 or M % t:
+        raise ValueError(f'lsq_linear_xnor: bad sizes M={M} F={F} O={O} kx={kx} rows_per_scale={t}')
+    nw, kw = (F + 63) // 64, wscales.shape[0]
+    opad = (O + 15) // 16 * 16
+    if planes.numel() < kx * M * nw or xscales.numel() != kx * (M // t):
+        raise ValueError('lsq_linear_xnor: activation planes / scales do not match (kx, M, F)')
+    if wscales.dim() != 2 or wscales.shape[1] != O or wbits.numel() != kw * nw * opad or wsum.numel() != kw * O:
+        raise ValueError('lsq_linear_xnor: weight planes / sums / scales do not match (O, F)')
+    if bias is not None and bias.numel() != O:
+        raise ValueError('lsq_linear_xnor: bias must have O elements')
+    y = torch.empty((M, O), dtype=torch.float32, device=dev)
+    with _on(y), _Timed('lsq_linear_xnor', M * kx * nw * 8 + 4 * M * O, M * O * F * kx * kw):
+        check(linear_lib().lsq_linear_xnor(planes.data_ptr(), kx, xscales.data_ptr(), t, wbits.data_ptr(), wsum.data_ptr(),
+                                           kw, wscales.data_ptr(), ptr(bias), M, F, O, y.data_ptr(), stream_ptr(dev)),
+              'lsq_linear_xnor')
+    return y
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

@@ -1,0 +1,173 @@
+"""``QuantLinear``: fully connected layer of scaled-binary-quantized activations and weights.
+
+The linear counterpart of ``QuantConv2d``: the same schemes (fp | ls-1 | ls-2 | ls-T | gf-k), constructor arguments
+(``x_quant, w_quant, in_features, out_features, clamp, moving_average_mode, moving_average_momentum`` then ``bias``),
+attributes (``x_approximate``, ``w_approximate``, ``clamping_fn``, ``quantized_parameters``), quantizer buffer names and
+``ValueError``s; the factories are ``QuantConv2d``'s own.
+
+Semantics are those of the quantizer modules: an activation row is one SAMPLE, ``x.view(N, -1)`` in x's own element
+order, quantized on the 4-D view ``(N, T*F, 1, 1)`` (T = the product of the dimensions between the batch and the
+features); a weight row is one output feature, quantized on ``(O, F, 1, 1)``.  Input ``[N, F]`` or ``[N, *, F]``,
+output ``[N, O]`` or ``[N, *, O]``.
+
+Dispatch of ``forward``:
+  * CUDA fp32 tensor, ``eval()`` mode, no gradient wanted for the input, binary schemes on both sides, T == 1 or
+    F % 64 == 0 -> lsq_act_quant on (N, T*F, 1, 1), weight sign planes packed once per ``eval()`` session, then the fp4
+    matrix-core GEMM lsq_linear_xnor (liblsq_hip_linear.so).  No fallback on this branch: a failed launch raises.
+  * anything else (CPU, training, ``fp`` on either side, F % 64 != 0 with T > 1, beyond the kernels' limits) -> the
+    torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on the same 4-D views.
+"""
+
+from collections import defaultdict
+from typing import Any, Dict, List, Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from quant.binary.binary_conv import QuantConv2d
+
+
+class QuantLinear(nn.Linear):
+    """``Linear(x_quant(clamp(x)), w_quant(w))`` with schemes fp | ls-1 | ls-2 | ls-T | gf-k."""
+
+    #: sub-sampling stride of the activation v1 search (as QuantConv2d)
+    act_skip = QuantConv2d.act_skip
+
+    def __init__(self, x_quant: str, w_quant: str, in_features: int, out_features: int, clamp: Optional[Dict] = None,
+                 moving_average_mode: str = 'off', moving_average_momentum: float = 0.99, bias: bool = True) -> None:
+        super().__init__(in_features, out_features, bias=bias)
+        self.x_quant, self.w_quant = x_quant, w_quant
+        self.x_approximate = QuantConv2d._get_x_quantizer(x_quant, moving_average_mode, moving_average_momentum)
+        self.w_approximate = QuantConv2d._get_w_quantizer(w_quant, out_features)
+        self.clamp_config = dict(clamp) if clamp is not None else {'kind': 'identity'}
+        self.clamping_fn = QuantConv2d._get_clamper(**self.clamp_config)
+
+        self.quantized_parameters: Dict[str, List[torch.Tensor]] = defaultdict(list)
+        if self.bias is not None:
+            self.quantized_parameters['fp'].append(self.bias)
+        self.quantized_parameters[w_quant].append(self.weight)
+
+        self._hip_cache: Dict[str, Any] = {}          # packed weights, plane workspaces (never in state_dict)
+
+    _alpha = QuantConv2d._alpha                       # symmetric clamp bound, or -1 for the identity
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._wants_hip(x):
+            return self._forward_hip(x)
+        return self._forward_torch(x)
+
+    def _rows(self, x: torch.Tensor):
+        """(N, T): samples and rows per sample of an input [N, *, F]."""
+        if x.dim() < 2 or x.shape[-1] != self.in_features:
+            raise ValueError(f'QuantLinear expects [N, *, {self.in_features}], got {list(x.shape)}')
+        n = x.shape[0]
+        t = 1
+        for s in x.shape[1:-1]:
+            t *= s
+        return n, t
+
+    def _forward_torch(self, x: torch.Tensor) -> torch.Tensor:
+        n, t = self._rows(x)
+        f, o = self.in_features, self.out_features
+        x_q = self.x_approximate(self.clamping_fn(x.reshape(n, t * f, 1, 1))).reshape(x.shape)
+        w_q = self.w_approximate(self.weight.view(o, f, 1, 1)).view(o, f)
+        return F.linear(x_q, w_q, self.bias)
+
+    def _wants_hip(self, x: torch.Tensor) -> bool:
+        if not x.is_cuda or self.training:
+            return False
+        if torch.is_grad_enabled() and x.requires_grad:
+            return False
+        if self.x_quant == 'fp' or self.w_quant == 'fp':
+            return False
+        if x.dim() < 2 or x.shape[-1] != self.in_features or x.numel() == 0:
+            return False
+        return self._hip_supports(x)
+
+    def _hip_supports(self, x: torch.Tensor) -> bool:
+        """The limits of lsq_act_quant and lsq_linear_xnor; anything outside them takes the torch formulation."""
+        from quant import _hip
+        if x.dtype != torch.float32 or self.weight.dtype != torch.float32:
+            return False
+        if getattr(self.w_approximate, 'k', 1) > _hip.MAX_PLANES or self.x_approximate.n_planes > _hip.MAX_PLANES:
+            return False
+        n, t = self._rows(x)
+        f, row = self.in_features, t * self.in_features
+        if t > 1 and f % 64:
+            return False                  # the rows of a sample must start on whole plane words
+        if f >= _hip.LINEAR_MAX_FEATURES or self.out_features >= _hip.LINEAR_MAX_OUTPUTS or row >= 1 << 31 or n * t >= 1 << 31:
+            return False
+        if self.x_quant in ('ls-2', 'ls-T') and (row + self.act_skip - 1) // self.act_skip >= _hip.MAX_SOLVER_KEYS:
+            return False
+        return True
+
+    def _replicate_for_data_parallel(self):
+        replica = super()._replicate_for_data_parallel()
+        replica._hip_cache = {}
+        return replica
+
+    def train(self, mode: bool = True):
+        if mode:
+            self._hip_cache.clear()       # weights (and cached scales) may change
+        return super().train(mode)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._hip_cache.clear()
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        self._hip_cache.clear()
+        return super()._apply(fn, *args, **kwargs)
+
+    # ------------------------------------------------------------------ HIP path
+    def _packed_weights(self, _hip):
+        """Weight sign planes of (O, F, 1, 1), packed once per eval session (re-packed when the weight or a scale changes)."""
+        wq = self.w_approximate
+        bufs = wq.cached_scales()
+        w = self._parameters['weight']
+        stamp = (w._version, w.data_ptr()) + tuple((b._version, b.data_ptr()) for b in bufs)
+        hit = self._hip_cache.get('w')
+        if hit is None or hit[0] != stamp:
+            o, f = self.out_features, self.in_features
+            geom = _hip.make_geom(1, f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
+            scales = wq.plane_scales().to(torch.float32).contiguous()
+            wbits, wsum = _hip.pack_weight(self.weight.detach().view(o, f, 1, 1), geom, scales)
+            hit = (stamp, wbits, wsum.view(scales.shape[0], o), scales)
+            self._hip_cache['w'] = hit
+        return hit[1], hit[2], hit[3]
+
+    def _act_planes(self, x2, geom, k, _hip):
+        """lsq_act_quant of the rows ``x2`` [N, T*F] into this module's plane workspace; returns (planes, scales)."""
+        n = geom.N
+        key = ('act', geom.key()[:4], k, x2.device, _hip.stream_ptr(x2.device))
+        ws = self._hip_cache.get(key)
+        if ws is None:
+            ws = (torch.zeros((k * _hip.act_plane_words(geom),), dtype=torch.int64, device=x2.device),
+                  torch.empty((k, n), dtype=torch.float32, device=x2.device))
+            stale = [kk for kk in list(self._hip_cache) if isinstance(kk, tuple) and kk[0] == 'act']
+            for kk in stale[:max(0, len(stale) - 3)]:
+                self._hip_cache.pop(kk, None)
+            self._hip_cache[key] = ws
+        planes, scales = ws
+        xq = self.x_approximate
+        forced = xq.eval_scales(n)
+        if forced is not None:
+            forced = forced.to(device=x2.device, dtype=torch.float32).contiguous()
+        _hip.act_quant(x2, geom, xq.hip_scheme, k, self.act_skip, self._alpha(), planes, scales, forced)
+        return planes, scales
+
+    def _forward_hip(self, x: torch.Tensor) -> torch.Tensor:
+        from quant import _hip
+        x = x.detach()
+        n, t = self._rows(x)
+        f, o = self.in_features, self.out_features
+        geom = _hip.make_geom(n, t * f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
+        wbits, wsum, wscales = self._packed_weights(_hip)
+        k = self.x_approximate.n_planes
+        planes, scales = self._act_planes(x.reshape(n, t * f), geom, k, _hip)
+        bias = None if self.bias is None else self.bias.detach()
+        y = _hip.linear_xnor(planes, k, scales, t, wbits, wsum, wscales, bias, n * t, f, o)
+        self.last_act_scales = scales
+        return y.view(*x.shape[:-1], o)

@@ -3,6 +3,7 @@
 Same constructor, sub-module names and forward as the reference's ``quant/models/lenet.py``
 (:21-94): first and last layers full precision, ``conv2`` a 5x5 ``QuantConv2d`` over 20
 input channels (not a multiple of 64, no padding) fed by a non-affine batch norm.
+One optional keyword of this project's own, ``fc1_quant``, makes ``fc1`` a ``QuantLinear``.
 """
 
 from typing import Callable, Dict, Optional
@@ -12,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from quant.binary.binary_conv import QuantConv2d
+from quant.binary.binary_linear import QuantLinear
 
 
 class QLeNet5(nn.Module):
@@ -20,7 +22,9 @@ class QLeNet5(nn.Module):
     def __init__(self, loss_fn: Callable[..., torch.Tensor], conv1_filters: int = 20, conv2_filters: int = 50,
                  output_classes: int = 10, x_quant: str = 'fp', w_quant: str = 'fp',
                  clamp: Optional[Dict] = None, moving_average_mode: str = 'off',
-                 moving_average_momentum: float = 0.99) -> None:
+                 moving_average_momentum: float = 0.99, fc1_quant: Optional[Dict] = None) -> None:
+        """``fc1_quant``: None (``fc1`` full precision, as in the reference), or ``{'x_quant', 'w_quant'[, 'clamp']}`` for a
+        binary ``fc1`` (``QuantLinear``, 800 -> 500 with the default sizes; moving-average settings as ``conv2``'s)."""
         super().__init__()
         setattr(self, 'loss_fn', loss_fn)
         self.conv1_filters, self.conv2_filters = conv1_filters, conv2_filters
@@ -33,7 +37,11 @@ class QLeNet5(nn.Module):
                                  moving_average_mode, moving_average_momentum, stride=1)
         self.bn_conv2 = nn.BatchNorm2d(conv1_filters, eps=1e-4, momentum=0.1, affine=False)
         hidden = conv2_filters * output_classes
-        self.fc1 = nn.Linear(conv2_filters * 4 * 4, hidden)
+        if fc1_quant is None:
+            self.fc1 = nn.Linear(conv2_filters * 4 * 4, hidden)
+        else:
+            self.fc1 = QuantLinear(fc1_quant['x_quant'], fc1_quant['w_quant'], conv2_filters * 4 * 4, hidden,
+                                   fc1_quant.get('clamp'), moving_average_mode, moving_average_momentum)
         self.fc2 = nn.Linear(hidden, output_classes)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
