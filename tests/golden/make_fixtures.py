@@ -90,6 +90,11 @@ def f24_quantizers():
     out.update(gf2_v1=vs[0], gf2_v2=vs[1], gf2_xq=xq)
     vs, xq = r_q.quantizer_gf(x, 3)
     out.update(gf3_v1=vs[0], gf3_v2=vs[1], gf3_v3=vs[2], gf3_b=packbits(torch.sign(xq)))
+    # LSQ_MAX_PLANES deep: the scales, the sign of x_q and every sign plane, plane q = sign(x - result_q) with result_q the
+    # reference's own q-plane result under the same scales
+    vs, xq = r_q.quantizer_gf(x, 8)
+    out.update({f'gf8_v{i + 1}': v for i, v in enumerate(vs)}, gf8_b=packbits(torch.sign(xq)))
+    out.update(gf8_planes=np.stack([packbits(r_sign(x - r_q.quantizer_gf(x, q, vs[:q])[1])) for q in range(8)]))
     # injected scales (eval-mode / moving-average style calls)
     inj1 = detgen.uniform('f24.inj1', (4,), 0.6, 1.4)
     inj2 = detgen.uniform('f24.inj2', (4,), 0.2, 0.6)

@@ -133,7 +133,7 @@ def _chain(x, scales, alpha):
 
 
 @pytest.mark.parametrize('shape', [(5, 16, 6, 6), (3, 7, 5, 3), (24, 32, 3, 3), (2, 1, 1, 9)])
-@pytest.mark.parametrize('k', [0, 1, 2, 3])
+@pytest.mark.parametrize('k', range(9))
 def test_ste_kernels_equal_the_torch_chain(shape, k):
     """lsq_quant_values (bit for bit) and lsq_ste_backward (1e-6) against the chain in torch, for activations (clamp) and
     weight-shaped rows (no clamp), row lengths with and without 16-byte rows, +-0, values on the clamp and on the |d| = 1
@@ -160,7 +160,8 @@ def test_ste_kernels_equal_the_torch_chain(shape, k):
 
 
 TRAIN_CASES = [('ls-2', 'ls-1', 1, True), ('ls-1', 'ls-1', 2, True), ('gf-2', 'ls-1', 1, False), ('ls-T', 'ls-1', 2, True),
-               ('fp', 'ls-1', 1, True), ('ls-1', 'gf-2', 1, True), ('ls-1', 'ls-2', 2, False), ('ls-2', 'ls-T', 1, True)]
+               ('fp', 'ls-1', 1, True), ('ls-1', 'gf-2', 1, True), ('ls-1', 'ls-2', 2, False), ('ls-2', 'ls-T', 1, True),
+               ('gf-4', 'gf-3', 1, True), ('gf-4', 'gf-3', 2, False)]
 
 
 @pytest.mark.parametrize('xs,ws,stride,bias', TRAIN_CASES)

@@ -183,7 +183,8 @@ def test_resnet18_shapes_batch256_against_the_torch_formulation(c, o, h, s):
 
 # ---- QuantConv2d's train step
 BINARY_TRAIN_CASES = [('ls-2', 'ls-1', 1, True), ('ls-1', 'ls-1', 2, True), ('gf-2', 'ls-1', 1, False), ('ls-T', 'ls-1', 2, True),
-                      ('ls-1', 'gf-2', 1, True), ('ls-1', 'ls-2', 2, False), ('ls-2', 'ls-T', 1, True)]
+                      ('ls-1', 'gf-2', 1, True), ('ls-1', 'ls-2', 2, False), ('ls-2', 'ls-T', 1, True),
+                      ('gf-4', 'gf-3', 1, True), ('gf-4', 'gf-3', 2, False)]
 
 
 @pytest.fixture

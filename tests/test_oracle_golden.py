@@ -44,6 +44,23 @@ def test_quantizers_bit_exact(golden):
     assert torch.equal(P.quant_ls2(x, g['inj1'])[1], g['ls2_v2_from_inj1'])
 
 
+def test_gf8_bit_exact(golden):
+    """quant_gf at LSQ_MAX_PLANES = 8 planes: the eight scales, the sign of x_q and every sign plane of the result chain
+    (the planes the GPU tests take as their bit reference) equal the reference's, bit for bit."""
+    g = golden('f24_quantizers')
+    x = detgen.normal('f24.x', (4, 64, 14, 14), scale=1.3).clamp(-3, 3)
+    vs, xq = P.quant_gf(x, 8)
+    assert all(torch.equal(v, g[f'gf8_v{i + 1}']) for i, v in enumerate(vs))
+    assert np.array_equal(np.packbits((xq.numpy() > 0).astype(np.uint8).reshape(-1)), g.np('gf8_b'))
+    want, result = g.np('gf8_planes'), torch.zeros_like(x)
+    assert want.shape[0] == 8
+    for q, v in enumerate(vs):
+        b = P.pm1(x - result)
+        assert np.array_equal(np.packbits((b.numpy() > 0).astype(np.uint8).reshape(-1)), want[q]), q
+        result = result + v.view(-1, 1, 1, 1) * b
+    assert torch.equal(result, xq)
+
+
 def _solver_rows():
     rows = {'long': detgen.normal('f3.long', (4, 25088), scale=1.0).clamp(-3, 3),
             'relu': detgen.normal('f3.relu', (4, 3000)).clamp(min=0),
