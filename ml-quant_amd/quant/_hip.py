@@ -777,6 +777,72 @@ def linear_xnor(planes: torch.Tensor, kx: int, xscales: torch.Tensor, rows_per_s
     return y
 
 
+# ---- the fp-activation linear-layer library (include/lsq_hip_linear_fp.h): a fourth shared object, loaded on first use
+_LINEAR_FP_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib', 'liblsq_hip_linear_fp.so')
+LINEAR_FP_ABI_VERSION = 1
+_linear_fp_lib = None
+
+
+def linear_fp_library_path() -> str:
+    return _LINEAR_FP_LIB_PATH
+
+
+def linear_fp_lib():
+    """Load (once) and return the fp-activation linear-layer library; raises if it has not been built (no fallback, as
+    ``lib()``)."""
+    global _linear_fp_lib
+    if _linear_fp_lib is None:
+        with _lock:
+            if _linear_fp_lib is None:
+                if not os.path.exists(_LINEAR_FP_LIB_PATH):
+                    raise LsqHipError(
+                        f'{_LINEAR_FP_LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
+                        '(or `make -C ml-quant_amd/csrc/linear_fp`). The HIP path has no fallback.')
+                handle = ctypes.CDLL(_LINEAR_FP_LIB_PATH)
+                vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+                handle.lsq_linear_fp_abi_version.restype = i32
+                handle.lsq_linear_fp_abi_version.argtypes = []
+                handle.lsq_linear_signw.restype = i32
+                handle.lsq_linear_signw.argtypes = [vp, f32, vp, i32, vp, vp, i64, i64, i64, vp, vp]
+                if handle.lsq_linear_fp_abi_version() != LINEAR_FP_ABI_VERSION:
+                    raise LsqHipError('liblsq_hip_linear_fp.so ABI version mismatch')
+                _linear_fp_lib = handle
+    return _linear_fp_lib
+
+
+def linear_signw(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: torch.Tensor, bias: Optional[torch.Tensor],
+                 M: int, F: int, O: int) -> torch.Tensor:
+    """y [M, O] = F.linear(clamp(x), w_q, bias) for fp32 rows ``x`` [M, F] (any 4-byte-aligned data pointer) and the sign
+    planes ``wbits`` / scales ``wscales`` [kw, O] lsq_pack_weight took and wrote for (O, F, 1, 1) (lsq_linear_signw);
+    ``alpha`` is the symmetric clamp bound, negative for none."""
+    if x.dtype != torch.float32 or wscales.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        raise TypeError('x, wscales and bias are fp32 tensors')
+    if wbits.dtype != torch.int64:
+        raise TypeError('wbits is an int64 tensor')
+    tensors = [x, wbits, wscales] + ([] if bias is None else [bias])
+    dev = x.device
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError('lsq_linear_signw: every operand on the same cuda device')
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError('lsq_linear_signw: operands must be contiguous')
+    M, F, O = int(M), int(F), int(O)
+    if min(M, F, O) <= 0 or x.numel() != M * F:
+        raise ValueError(f'lsq_linear_signw: bad sizes M={M} F={F} O={O} for x of {x.numel()} elements')
+    nw, opad = (F + 63) // 64, (O + 15) // 16 * 16
+    kw = wscales.shape[0] if wscales.dim() == 2 else 0
+    if wscales.dim() != 2 or wscales.shape[1] != O or wbits.numel() != kw * nw * opad:
+        raise ValueError('lsq_linear_signw: weight planes / scales do not match (O, F)')
+    if bias is not None and bias.numel() != O:
+        raise ValueError('lsq_linear_signw: bias must have O elements')
+    y = torch.empty((M, O), dtype=torch.float32, device=dev)
+    launches = (kw + 1) // 2                         # (y is read back by every launch after the first)
+    with _on(y), _Timed('lsq_linear_signw', 4 * M * F * launches + 8 * kw * nw * opad + 4 * M * O * (2 * launches - 1),
+                        2 * 2 * M * F * O * kw):       # bf16 FLOPs: the hi and the lo pass of every plane
+        check(linear_fp_lib().lsq_linear_signw(x.data_ptr(), float(alpha), wbits.data_ptr(), kw, wscales.data_ptr(),
+                                               ptr(bias), M, F, O, y.data_ptr(), stream_ptr(dev)), 'lsq_linear_signw')
+    return y
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

@@ -14,8 +14,11 @@ Dispatch of ``forward``:
   * CUDA fp32 tensor, ``eval()`` mode, no gradient wanted for the input, binary schemes on both sides, T == 1 or
     F % 64 == 0 -> lsq_act_quant on (N, T*F, 1, 1), weight sign planes packed once per ``eval()`` session, then the fp4
     matrix-core GEMM lsq_linear_xnor (liblsq_hip_linear.so).  No fallback on this branch: a failed launch raises.
-  * anything else (CPU, training, ``fp`` on either side, F % 64 != 0 with T > 1, beyond the kernels' limits) -> the
-    torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on the same 4-D views.
+  * the same conditions with ``fp`` activations and binary weights (any T and F) -> the weight sign planes packed once per
+    ``eval()`` session, then lsq_linear_signw (liblsq_hip_linear_fp.so): the clamp fused, the fp32 rows split into bf16
+    hi + lo on the bf16 matrix cores.  No fallback on this branch either.
+  * anything else (CPU, training, ``fp`` weights, F % 64 != 0 with T > 1 for binary activations, beyond the kernels'
+    limits) -> the torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on the same 4-D views.
 """
 
 from collections import defaultdict
@@ -80,17 +83,22 @@ class QuantLinear(nn.Linear):
             return False
         if torch.is_grad_enabled() and x.requires_grad:
             return False
-        if self.x_quant == 'fp' or self.w_quant == 'fp':
+        if self.w_quant == 'fp':
             return False
         if x.dim() < 2 or x.shape[-1] != self.in_features or x.numel() == 0:
             return False
         return self._hip_supports(x)
 
     def _hip_supports(self, x: torch.Tensor) -> bool:
-        """The limits of lsq_act_quant and lsq_linear_xnor; anything outside them takes the torch formulation."""
+        """The limits of lsq_act_quant and lsq_linear_xnor (binary activations) or of lsq_linear_signw (fp activations);
+        anything outside them takes the torch formulation."""
         from quant import _hip
         if x.dtype != torch.float32 or self.weight.dtype != torch.float32:
             return False
+        if self.x_quant == 'fp':
+            n, t = self._rows(x)
+            return (getattr(self.w_approximate, 'k', 1) <= _hip.MAX_PLANES and self.in_features < _hip.LINEAR_MAX_FEATURES
+                    and self.out_features < _hip.LINEAR_MAX_OUTPUTS and n * t < 1 << 31)
         if getattr(self.w_approximate, 'k', 1) > _hip.MAX_PLANES or self.x_approximate.n_planes > _hip.MAX_PLANES:
             return False
         n, t = self._rows(x)
@@ -163,11 +171,15 @@ class QuantLinear(nn.Linear):
         x = x.detach()
         n, t = self._rows(x)
         f, o = self.in_features, self.out_features
-        geom = _hip.make_geom(n, t * f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
         wbits, wsum, wscales = self._packed_weights(_hip)
+        bias = None if self.bias is None else self.bias.detach()
+        if self.x_quant == 'fp':
+            # (the kernel reads whole rows: a strided input -- h[:, 0], a slice of a wider tensor -- is copied first)
+            y = _hip.linear_signw(x.reshape(n * t, f).contiguous(), self._alpha(), wbits, wscales, bias, n * t, f, o)
+            return y.view(*x.shape[:-1], o)
+        geom = _hip.make_geom(n, t * f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
         k = self.x_approximate.n_planes
         planes, scales = self._act_planes(x.reshape(n, t * f), geom, k, _hip)
-        bias = None if self.bias is None else self.bias.detach()
         y = _hip.linear_xnor(planes, k, scales, t, wbits, wsum, wscales, bias, n * t, f, o)
         self.last_act_scales = scales
         return y.view(*x.shape[:-1], o)
