@@ -843,6 +843,86 @@ def linear_signw(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: to
     return y
 
 
+# ---- the linear-layer training library (include/lsq_hip_linear_train.h): a fifth shared object, loaded on first use
+_LINEAR_TRAIN_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib',
+                                      'liblsq_hip_linear_train.so')
+LINEAR_TRAIN_ABI_VERSION = 1
+_linear_train_lib = None
+
+
+def linear_train_library_path() -> str:
+    return _LINEAR_TRAIN_LIB_PATH
+
+
+def linear_train_lib():
+    """Load (once) and return the linear-layer training library; raises if it has not been built (no fallback, as
+    ``lib()``)."""
+    global _linear_train_lib
+    if _linear_train_lib is None:
+        with _lock:
+            if _linear_train_lib is None:
+                path = linear_train_library_path()
+                if not os.path.exists(path):
+                    raise LsqHipError(
+                        f'{path} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
+                        '(or `make -C ml-quant_amd/csrc/linear_train`). The HIP path has no fallback.')
+                handle = ctypes.CDLL(path)
+                vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+                handle.lsq_linear_train_abi_version.restype = i32
+                handle.lsq_linear_train_abi_version.argtypes = []
+                handle.lsq_linear_signw_dgrad_workspace_bytes.restype = ctypes.c_size_t
+                handle.lsq_linear_signw_dgrad_workspace_bytes.argtypes = [i32, i64, i64]
+                handle.lsq_linear_signw_dgrad.restype = i32
+                handle.lsq_linear_signw_dgrad.argtypes = [vp, vp, i32, vp, i64, i64, i64, vp, vp, ctypes.c_size_t, vp]
+                if handle.lsq_linear_train_abi_version() != LINEAR_TRAIN_ABI_VERSION:
+                    raise LsqHipError('liblsq_hip_linear_train.so ABI version mismatch')
+                _linear_train_lib = handle
+    return _linear_train_lib
+
+
+_dgrad_ws_cache = {}
+
+
+def linear_signw_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Tensor, M: int, F: int, O: int) -> torch.Tensor:
+    """gx [M, F] = gy @ w_q for fp32 gradient rows ``gy`` [M, O] (any 4-byte-aligned data pointer) and the sign planes
+    ``wbits`` / scales ``wscales`` [kw, O] lsq_pack_weight took and wrote for (O, F, 1, 1) -- the forward's own operands
+    (lsq_linear_signw_dgrad).  The transposed plane image lives in a workspace cached per (device, stream) like the
+    solver's (rewritten by every call; kernels of one stream run in order)."""
+    if gy.dtype != torch.float32 or wscales.dtype != torch.float32:
+        raise TypeError('gy and wscales are fp32 tensors')
+    if wbits.dtype != torch.int64:
+        raise TypeError('wbits is an int64 tensor')
+    tensors = [gy, wbits, wscales]
+    dev = gy.device
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError('lsq_linear_signw_dgrad: operands must be contiguous')
+    M, F, O = int(M), int(F), int(O)
+    if min(M, F, O) <= 0 or gy.numel() != M * O:
+        raise ValueError(f'lsq_linear_signw_dgrad: bad sizes M={M} F={F} O={O} for gy of {gy.numel()} elements')
+    nw, opad = (F + 63) // 64, (O + 15) // 16 * 16
+    kw = wscales.shape[0] if wscales.dim() == 2 else 0
+    if wscales.dim() != 2 or wscales.shape[1] != O or wbits.numel() != kw * nw * opad:
+        raise ValueError('lsq_linear_signw_dgrad: weight planes / scales do not match (O, F)')
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError('lsq_linear_signw_dgrad: every operand on the same cuda device')
+    tl = linear_train_lib()
+    need = int(tl.lsq_linear_signw_dgrad_workspace_bytes(kw, F, O))
+    ws = None
+    if need:
+        key = (dev.index, stream_ptr(dev))
+        ws = _dgrad_ws_cache.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+            _remember(_dgrad_ws_cache, key, ws)
+    gx = torch.empty((M, F), dtype=torch.float32, device=dev)
+    with _on(gx), _Timed('lsq_linear_signw_dgrad', 4 * M * O * kw + 8 * kw * nw * opad + 2 * need + 4 * M * F,
+                         2 * 2 * M * F * O * kw):       # bf16 FLOPs: the hi and the lo pass of every plane
+        check(tl.lsq_linear_signw_dgrad(gy.data_ptr(), wbits.data_ptr(), kw, wscales.data_ptr(), M, F, O, gx.data_ptr(),
+                                        ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev)),
+              'lsq_linear_signw_dgrad')
+    return gx
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

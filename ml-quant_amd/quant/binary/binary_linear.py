@@ -17,8 +17,13 @@ Dispatch of ``forward``:
   * the same conditions with ``fp`` activations and binary weights (any T and F) -> the weight sign planes packed once per
     ``eval()`` session, then lsq_linear_signw (liblsq_hip_linear_fp.so): the clamp fused, the fp32 rows split into bf16
     hi + lo on the bf16 matrix cores.  No fallback on this branch either.
-  * anything else (CPU, training, ``fp`` weights, F % 64 != 0 with T > 1 for binary activations, beyond the kernels'
-    limits) -> the torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on the same 4-D views.
+  * CUDA fp32 tensor in ``train()`` mode with ``hip_train`` set (class attribute, False by default), binary weights and
+    the same limits -> the kernels of the inference path for the forward and ``quant.binary.hip_train_linear`` for the
+    backward (lsq_linear_signw_dgrad of liblsq_hip_linear_train.so, straight-through estimator), one
+    ``torch.autograd.Function`` per call.
+  * anything else (CPU, training without ``hip_train``, ``fp`` weights, F % 64 != 0 with T > 1 for binary activations,
+    beyond the kernels' limits) -> the torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on
+    the same 4-D views.
 """
 
 from collections import defaultdict
@@ -56,9 +61,17 @@ class QuantLinear(nn.Linear):
     _alpha = QuantConv2d._alpha                       # symmetric clamp bound, or -1 for the identity
 
     # ------------------------------------------------------------------ forward
+    #: train-mode CUDA tensors through the kernels (quant.binary.hip_train_linear).  False: the torch formulation, the
+    #: default until the measured train step says otherwise
+    hip_train = False
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
             return self._forward_hip(x)
+        if self.training and self.hip_train and x.is_cuda:
+            from quant.binary import hip_train_linear
+            if hip_train_linear.supported(self, x):
+                return hip_train_linear.train_step_forward(self, x)
         return self._forward_torch(x)
 
     def _rows(self, x: torch.Tensor):

@@ -1,0 +1,133 @@
+"""Train-mode ``QuantLinear`` on the gfx950 kernels: the counterpart of ``quant.binary.hip_train`` for the linear layer.
+
+The torch formulation (``QuantLinear._forward_torch``) trains through stock autograd: the clamp, the activation quantizer
+(scales from detached data, signs through ``STESign``), the weight quantizer in its compute-and-cache mode and
+``F.linear`` over fp32 ``x_q`` and ``w_q``.  Here the same step is one ``torch.autograd.Function`` around the C ABI, for an
+input ``[N, F]`` or ``[N, *, F]`` (T = the product of the middle dimensions, M = N * T rows):
+
+forward   the weight scales are computed from the detached weight and cached (``copy_`` into the ``v1..vk`` buffers, as
+          the torch formulation does in train mode); ``lsq_pack_weight`` packs this step's sign planes;
+          binary activations: ``lsq_act_quant`` on (N, T*F, 1, 1) solves the per-sample scales and packs the planes, then
+          ``lsq_linear_xnor``; fp activations: ``lsq_linear_signw`` (clamp fused) -- the kernels of the inference path.
+          Saved for backward: the input, the weight, both sets of scales and the weight planes -- tensors of the step, so
+          a second forward of the same module before backward changes nothing backward reads.
+backward  grad_bias = sum over the rows of grad_y;
+          grad_xq   = grad_y . w_q: ``lsq_linear_signw_dgrad`` (liblsq_hip_linear_train.so) from the forward's own weight
+                      planes, one bit per weight;
+          grad_x    = ``lsq_ste_backward`` over the sample rows (N, T*F): straight-through estimator of every sign of the
+                      quantizer chain + clamp mask;
+          grad_wq   = grad_y^T x_q with x_q = ``lsq_quant_values`` (fp activations: the clamp's value) on ``torch.mm`` -- the
+                      library route ``hip_train`` takes by default for the convolution;
+          grad_w    = ``lsq_ste_backward`` over the weight rows.
+Nothing is computed for an input that needs no gradient.  Results are those of the torch formulation within fp32
+reassociation and the bf16 hi + lo split of the kernels (tests: test_gpu_linear_train.py).
+"""
+
+import os
+
+import torch
+from torch.autograd.function import once_differentiable
+
+
+def supported(lin, x: torch.Tensor) -> bool:
+    """Train-mode forward + backward on the kernels: fp32 CUDA input ``[N, *, F]`` and weight, binary weights, the limits
+    of ``QuantLinear._hip_supports`` -- and the libraries built (without them a training run takes the torch formulation;
+    the eval path, by contrast, raises)."""
+    if not x.is_cuda or x.dtype != torch.float32 or lin.weight.dtype != torch.float32 or not lin.weight.is_cuda:
+        return False
+    if lin.w_quant == 'fp':
+        return False
+    if x.dim() < 2 or x.shape[-1] != lin.in_features or x.numel() == 0:
+        return False
+    from quant import _hip
+    if not _hip.available() or not os.path.exists(_hip.linear_train_library_path()):
+        return False
+    if not os.path.exists(_hip.linear_fp_library_path() if lin.x_quant == 'fp' else _hip.linear_library_path()):
+        return False
+    return lin._hip_supports(x)
+
+
+def _step_planes(lin, geom, k, device, _hip):
+    """The module's activation-plane workspace for train steps, one per row length and launch stream (the planes are
+    consumed by the forward GEMM alone: backward reads the saved scales, not the planes)."""
+    key = ('train_planes', geom.key()[:4], k, device, _hip.stream_ptr(device))
+    planes = lin._hip_cache.get(key)
+    if planes is None:
+        planes = torch.zeros((k * _hip.act_plane_words(geom),), dtype=torch.int64, device=device)
+        stale = [kk for kk in list(lin._hip_cache) if isinstance(kk, tuple) and kk[0] == 'train_planes']
+        for kk in stale[:max(0, len(stale) - 3)]:
+            lin._hip_cache.pop(kk, None)
+        lin._hip_cache[key] = planes
+    return planes
+
+
+class _QuantLinearStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, lin):
+        from quant import _hip
+        x = x.contiguous()
+        n, t = lin._rows(x)
+        f, o = lin.in_features, lin.out_features
+        m = n * t
+        alpha = lin._alpha()
+        # weight scales: computed from the detached weights and cached in the module's buffers (train mode)
+        with torch.no_grad():
+            lin.w_approximate(weight.detach().view(o, f, 1, 1))
+            wscales = lin.w_approximate.plane_scales().to(torch.float32).contiguous()           # [planes, O]
+        wgeom = _hip.make_geom(1, f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
+        wbits, wsum = _hip.pack_weight(weight.detach().view(o, f, 1, 1), wgeom, wscales)
+        b = None if bias is None else bias.detach()
+        xq_mod = lin.x_approximate
+        if lin.x_quant == 'fp':
+            y = _hip.linear_signw(x.detach().view(m, f), alpha, wbits, wscales, b, m, f, o)
+            xscales = None
+        else:
+            k = xq_mod.n_planes
+            geom = _hip.make_geom(n, t * f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
+            planes = _step_planes(lin, geom, k, x.device, _hip)
+            x2 = x.detach().view(n, t * f)
+            xscales = torch.empty((k, n), dtype=torch.float32, device=x.device)    # saved for backward: a tensor of this step
+            forced = xq_mod._forced_scales
+            forced = None if forced is None else xq_mod.plane_scales(forced).to(device=x.device, dtype=torch.float32).contiguous()
+            _hip.act_quant(x2, geom, xq_mod.hip_scheme, k, lin.act_skip, alpha, planes, xscales, forced)
+            # moving averages: tracked from the batch's mean scales; 'train_and_eval' quantizes with the tracked values
+            from quant.binary.activation_quantization import MovingAverageMode
+            if forced is None and xq_mod.moving_average_mode != MovingAverageMode.off:
+                with torch.no_grad():
+                    tracked = xq_mod.moving_avg_module(xscales[:xq_mod.num_scaling_factors].mean(1))
+                if xq_mod.moving_average_mode == MovingAverageMode.train_and_eval:
+                    forced = xq_mod.plane_scales(tracked.view(-1, 1).expand(-1, n)).to(torch.float32).contiguous()
+                    _hip.act_quant(x2, geom, xq_mod.hip_scheme, k, lin.act_skip, alpha, planes, xscales, forced)
+            y = _hip.linear_xnor(planes, k, xscales, t, wbits, wsum.view(wscales.shape[0], o), wscales, b, m, f, o)
+            lin.last_act_scales = xscales
+        ctx.alpha, ctx.dims = alpha, (n, t, f, o)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, weight, wscales, wbits, xscales if xscales is not None else x.new_empty(0))
+        return y.view(*x.shape[:-1], o)
+
+    @staticmethod
+    @once_differentiable                       # (the straight-through kernels have no second derivative: say so instead of returning a wrong one)
+    def backward(ctx, gy):
+        from quant import _hip
+        x, weight, wscales, wbits, xscales = ctx.saved_tensors
+        xscales = xscales if xscales.numel() else None
+        n, t, f, o = ctx.dims
+        m, alpha = n * t, ctx.alpha
+        gy2 = gy.reshape(m, o).contiguous()
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        gx = gw = gb = None
+        if need_b:
+            gb = gy2.sum(dim=0)
+        if need_x:
+            gxq = _hip.linear_signw_dgrad(gy2, wbits, wscales, m, f, o)
+            gx = _hip.ste_backward(x.view(n, t * f), gxq.view(n, t * f), xscales, alpha).view(x.shape)
+        if need_w:
+            xq = _hip.quant_values(x.view(n, t * f), xscales, alpha).view(m, f)
+            gwq = torch.mm(gy2.t(), xq)
+            gw = _hip.ste_backward(weight.detach(), gwq, wscales, -1.0)
+        return gx, gw, gb, None
+
+
+def train_step_forward(lin, x: torch.Tensor) -> torch.Tensor:
+    """``lin(x)`` in train mode through the kernels, differentiable with respect to x, weight and bias."""
+    return _QuantLinearStep.apply(x, lin.weight, lin.bias, lin)
