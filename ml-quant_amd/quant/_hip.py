@@ -923,6 +923,88 @@ def linear_signw_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Ten
     return gx
 
 
+# ---- the linear layer's weight-gradient library (include/lsq_hip_linear_wgrad.h): a sixth shared object, loaded on first use
+_LINEAR_WGRAD_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib',
+                                      'liblsq_hip_linear_wgrad.so')
+LINEAR_WGRAD_ABI_VERSION = 1
+LINEAR_WGRAD_MAX_SAMPLES = 65535    # lsq_linear_signx_wgrad: N <= 65535 (the limit of lsq_quant_values)
+_linear_wgrad_lib = None
+
+
+def linear_wgrad_library_path() -> str:
+    return _LINEAR_WGRAD_LIB_PATH
+
+
+def linear_wgrad_lib():
+    """Load (once) and return the linear layer's weight-gradient library; raises if it has not been built (no fallback, as
+    ``lib()``)."""
+    global _linear_wgrad_lib
+    if _linear_wgrad_lib is None:
+        with _lock:
+            if _linear_wgrad_lib is None:
+                path = linear_wgrad_library_path()
+                if not os.path.exists(path):
+                    raise LsqHipError(
+                        f'{path} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
+                        '(or `make -C ml-quant_amd/csrc/linear_wgrad`). The HIP path has no fallback.')
+                handle = ctypes.CDLL(path)
+                vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+                handle.lsq_linear_wgrad_abi_version.restype = i32
+                handle.lsq_linear_wgrad_abi_version.argtypes = []
+                handle.lsq_linear_signx_wgrad_workspace_bytes.restype = ctypes.c_size_t
+                handle.lsq_linear_signx_wgrad_workspace_bytes.argtypes = [i32, i64, i64, i64, i64]
+                handle.lsq_linear_signx_wgrad.restype = i32
+                handle.lsq_linear_signx_wgrad.argtypes = [vp, vp, i32, vp, ctypes.c_float, i64, i64, i64, i64, vp, vp,
+                                                          ctypes.c_size_t, vp]
+                if handle.lsq_linear_wgrad_abi_version() != LINEAR_WGRAD_ABI_VERSION:
+                    raise LsqHipError('liblsq_hip_linear_wgrad.so ABI version mismatch')
+                _linear_wgrad_lib = handle
+    return _linear_wgrad_lib
+
+
+_linear_wgrad_ws_cache = {}
+
+
+def linear_signx_wgrad(gy: torch.Tensor, x: torch.Tensor, xscales: torch.Tensor, alpha: float, N: int, T: int, F: int,
+                       O: int) -> torch.Tensor:
+    """gwq [O, F] = gy^T @ x_q for fp32 gradient rows ``gy`` [N * T, O] (any 4-byte-aligned data pointer), the layer's input
+    ``x`` [N * T, F] before the clamp and the per-(plane, sample) scales ``xscales`` [kx, N] of its quantizer
+    (lsq_linear_signx_wgrad): x_q is never written, its signs go into a bit image in a workspace cached per (device, stream)
+    like the solver's (rewritten by every call; kernels of one stream run in order)."""
+    if gy.dtype != torch.float32 or x.dtype != torch.float32 or xscales.dtype != torch.float32:
+        raise TypeError('gy, x and xscales are fp32 tensors')
+    tensors = [gy, x, xscales]
+    dev = gy.device
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError('lsq_linear_signx_wgrad: operands must be contiguous')
+    N, T, F, O = int(N), int(T), int(F), int(O)
+    M = N * T
+    if min(N, T, F, O) <= 0 or gy.numel() != M * O or x.numel() != M * F:
+        raise ValueError(f'lsq_linear_signx_wgrad: bad sizes N={N} T={T} F={F} O={O} for gy of {gy.numel()} and x of '
+                         f'{x.numel()} elements')
+    kx = xscales.shape[0] if xscales.dim() == 2 else 0
+    if xscales.dim() != 2 or xscales.shape[1] != N:
+        raise ValueError('lsq_linear_signx_wgrad: activation scales do not match (kx, N)')
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError('lsq_linear_signx_wgrad: every operand on the same cuda device')
+    wl = linear_wgrad_lib()
+    need = int(wl.lsq_linear_signx_wgrad_workspace_bytes(kx, N, T, F, O))
+    ws = None
+    if need:
+        key = (dev.index, stream_ptr(dev))
+        ws = _linear_wgrad_ws_cache.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+            _remember(_linear_wgrad_ws_cache, key, ws)
+    gwq = torch.empty((O, F), dtype=torch.float32, device=dev)
+    with _on(gwq), _Timed('lsq_linear_signx_wgrad', 4 * M * O + 4 * M * F + 4 * kx * N + 2 * need + 4 * O * F,
+                          2 * 2 * M * F * O * kx):       # bf16 FLOPs: the hi and the lo pass of every plane
+        check(wl.lsq_linear_signx_wgrad(gy.data_ptr(), x.data_ptr(), kx, xscales.data_ptr(), float(alpha), N, T, F, O,
+                                        gwq.data_ptr(), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev)),
+              'lsq_linear_signx_wgrad')
+    return gwq
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

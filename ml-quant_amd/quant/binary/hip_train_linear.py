@@ -17,7 +17,9 @@ backward  grad_bias = sum over the rows of grad_y;
           grad_x    = ``lsq_ste_backward`` over the sample rows (N, T*F): straight-through estimator of every sign of the
                       quantizer chain + clamp mask;
           grad_wq   = grad_y^T x_q with x_q = ``lsq_quant_values`` (fp activations: the clamp's value) on ``torch.mm`` -- the
-                      library route ``hip_train`` takes by default for the convolution;
+                      library route ``hip_train`` takes by default for the convolution; with ``WGRAD_KERNEL`` and binary
+                      activations ``lsq_linear_signx_wgrad`` (liblsq_hip_linear_wgrad.so) from the input's sign bits
+                      instead: no x_q is written (DESIGN 4.13);
           grad_w    = ``lsq_ste_backward`` over the weight rows.
 Nothing is computed for an input that needs no gradient.  Results are those of the torch formulation within fp32
 reassociation and the bf16 hi + lo split of the kernels (tests: test_gpu_linear_train.py).
@@ -27,6 +29,11 @@ import os
 
 import torch
 from torch.autograd.function import once_differentiable
+
+# True: the weight gradient of a layer with binary activations runs on lsq_linear_signx_wgrad (sign image + bf16 hi + lo
+# GEMM on the matrix cores) instead of lsq_quant_values + torch.mm -- the counterpart of hip_train.WGRAD_KERNEL; DESIGN 4.13
+# has the measurements.  fp activations keep torch.mm under either setting.
+WGRAD_KERNEL = False
 
 
 def supported(lin, x: torch.Tensor) -> bool:
@@ -122,8 +129,11 @@ class _QuantLinearStep(torch.autograd.Function):
             gxq = _hip.linear_signw_dgrad(gy2, wbits, wscales, m, f, o)
             gx = _hip.ste_backward(x.view(n, t * f), gxq.view(n, t * f), xscales, alpha).view(x.shape)
         if need_w:
-            xq = _hip.quant_values(x.view(n, t * f), xscales, alpha).view(m, f)
-            gwq = torch.mm(gy2.t(), xq)
+            if WGRAD_KERNEL and xscales is not None and os.path.exists(_hip.linear_wgrad_library_path()):
+                gwq = _hip.linear_signx_wgrad(gy2, x.view(m, f), xscales, alpha, n, t, f, o)
+            else:
+                xq = _hip.quant_values(x.view(n, t * f), xscales, alpha).view(m, f)
+                gwq = torch.mm(gy2.t(), xq)
             gw = _hip.ste_backward(weight.detach(), gwq, wscales, -1.0)
         return gx, gw, gb, None
 
