@@ -35,10 +35,10 @@ int lsq_linear_fp_abi_version(void);
  *   bias        [O] fp32 or NULL
  *   y           out, [M][O] fp32; nothing outside it is written
  * Accuracy: each clamped activation v is split into hi = bf16(v) and lo = bf16(v - hi) (v - hi is exact in fp32, so
- * |v - hi - lo| <= 2^-18 |v|); the weights are exact +-1 in bf16, every product hi * s and lo * s is exact, and the
- * products are summed in fp32 by v_mfma_f32_32x32x16_bf16.  I_q therefore differs from the exact sum by at most
- * 2^-18 sum_f |c(x[m][f])| plus the fp32 rounding of the accumulation -- a single bf16 operand (2^-9 per product) would be
- * 2^9 times coarser.
+ * |v - hi - lo| <= 2^-16 |v|, typically 2^-18 |v|); the weights are exact +-1 in bf16, every product hi * s and lo * s is
+ * exact, and the products are summed in fp32 by v_mfma_f32_32x32x16_bf16.  I_q therefore differs from the exact sum by at
+ * most 2^-16 sum_f |c(x[m][f])| (typically 2^-18) plus the fp32 rounding of the accumulation -- a single bf16 operand
+ * (2^-8 per product at most, typically 2^-9) would be 2^8 times coarser.
  * Summation order (fixed for given M, F, O: results are bitwise deterministic, no atomics): I_q accumulates 16 features
  * per MFMA step in feature order, the hi products of a step before its lo products; the small-M kernel adds the partial
  * I_q of its 8 waves' feature ranges in wave order, ((I^0 + I^1) + I^2) + ...; the epilogue is

@@ -52,8 +52,6 @@ int lsq_linear_train_abi_version(void);
  * in the worst case (every a at the bottom of a binade with both roundings at half an ulp); the dropped terms are
  * independent of each other, and what is measured against fp64 is 2-4e-6 of max |gx| (tests/test_gpu_linear_train.py
  * holds every case to 1e-5 of it).  A single bf16 operand (2^-8 per product) is 2^8 times coarser and measures 2e-3.
- * (The figure 2^-18 that lsq_hip_linear_fp.h quotes for the same split is its typical size, not a bound: one product
- * already shows 1.6 * 2^-18.)
  * Summation order (fixed for given M, F, O, kw_planes: results are bitwise deterministic, no atomics): planes in order
  * q = 0 .. kw - 1, within a plane 16 output features per MFMA step in order of o, the hi products of a step before its lo
  * products, everything into one accumulator.  The small-shape kernel splits that sequence of (plane, 64-feature word)

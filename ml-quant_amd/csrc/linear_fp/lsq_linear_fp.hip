@@ -2,21 +2,17 @@
 //
 // As a GEMM:  I_q[m][o] = sum_f c(x[m][f]) s_q[o][f]  per weight plane q, M = rows, K = F features, N = O outputs, then
 // y = bias + sum_q ws[q][o] I_q.  Activations are operand A (rows m), weights operand B (columns o), the orientation of
-// csrc/linear/lsq_linear.hip: a lane of D holds ONE column o (lane & 31) and 16 rows, so a store instruction writes 32
-// consecutive floats of a row of y per half-wave.  Lane (r = lane & 31, h = lane >> 5) holds A[row r][k = 8 h + j] and
-// B[k = 8 h + j][col r] in element j = 0..7 of its fragments.
-//   * ACTIVATION: clamped (v_med3), split into hi = bf16(v) and lo = bf16(v - hi); two MFMAs per k-step (hi, then lo) into
-//     the same fp32 accumulator.  Features past F are staged as 0: they contribute 0 whatever the weight bits hold.
-//   * WEIGHT: the 8 sign bits of a lane's fragment (bits 16 s + 8 h .. + 7 of its column's plane word for k-step s) become
-//     8 bf16 +-1.0 in registers -- one packed 16-bit shift and one and-or per pair --, so the weight stream stays at one bit
-//     per weight (no 16-bit image in memory).  One accumulator per weight plane: ws[q][o] is per column AND plane.
+// csrc/linear/lsq_linear.hip; fragment layout, the hi / lo split and the sign-bit expansion: csrc/linear/lsq_signw_mma.h.
+//   * ACTIVATION: clamped (v_med3), then split.  Features past F are staged as 0: they contribute 0 whatever the weight
+//     bits hold.
+//   * WEIGHT: the plane words as lsq_pack_weight wrote them, so the weight stream stays at one bit per weight (no 16-bit
+//     image in memory).  One accumulator per weight plane: ws[q][o] is per column AND plane.
 //   * Rows past M and columns past O read a valid row / column and are never stored (a row of D depends only on its row of
 //     A, a column only on its column of B).
 // Two kernels behind the one entry point (selected from M and O, see lsq_linear_signw):
 //   signw_tiled  M x O tiles of 128 x 128 or 64 x 64 over the whole F, four waves (2 x 2); per stage of 64 features the
-//                workgroup splits its rows' activations ONCE into LDS (hi and lo rows of 144 bytes: 16-byte pad, conflict-
-//                free ds_read_b128 fragments); the next stage's activations and weight words are loaded into registers
-//                while the MFMAs of this one run.
+//                workgroup splits its rows' activations ONCE into LDS; the next stage's activations and weight words are
+//                loaded into registers while the MFMAs of this one run.
 //   signw_split  weight-streaming shapes (few rows): one 32 x 32 output tile per workgroup with its F split over 8 waves,
 //                each wave reading, splitting and multiplying its own feature range straight from global memory (every x
 //                element once per workgroup); the partial sums meet in LDS and are added in wave order.
@@ -28,19 +24,9 @@
 #include <stdint.h>
 
 #include "lsq_hip_linear_fp.h"
+#include "../linear/lsq_signw_mma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) unsigned short u16x2;
-
-union Frag {
-  unsigned u[4];
-  bf16x8 v;
-};
 
 struct Args {
   const float* x;                     // [M][F]
@@ -53,35 +39,6 @@ struct Args {
   float lim;                          // clamp bound (+inf: identity)
   int accumulate;                     // 0: base = bias (or 0); 1: base = y
 };
-
-constexpr int kPitch = 144;           // LDS bytes per staged row of signw_tiled: 64 bf16 + 16 bytes of pad
-constexpr int kSplitWaves = 8;        // waves of signw_split, one feature range each
-
-// v = hi + lo in bf16: hi = bf16(v) (round to nearest even), lo = bf16(v - hi); v - hi is exact in fp32, so
-// |v - hi - lo| <= 2^-18 |v|
-__device__ __forceinline__ void split_pair(float v0, float v1, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {v0, v1};
-  const bf16x2 h = __builtin_convertvector(v, bf16x2);
-  const f32x2 r = v - __builtin_convertvector(h, f32x2);
-  const bf16x2 l = __builtin_convertvector(r, bf16x2);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-
-// 8 sign bits (bit j set = +1) -> B fragment: element j = +-1.0 in bf16, half (j & 1) of dword j >> 1.  The inverted bits
-// in both 16-bit halves, one packed shift brings bit 2d / 2d + 1 to the sign position of the low / high half.
-__device__ __forceinline__ Frag expand8(unsigned bits) {
-  const unsigned short m = (unsigned short)(~bits & 0xFFu);
-  const u16x2 rep = {m, m};
-  Frag f;
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const u16x2 sh = {(unsigned short)(15 - 2 * d), (unsigned short)(14 - 2 * d)};
-    const u16x2 s = rep << sh;
-    f.u[d] = (__builtin_bit_cast(unsigned, s) & 0x80008000u) | 0x3F803F80u;
-  }
-  return f;
-}
 
 __device__ __forceinline__ float clampv(float v, float lim) { return __builtin_amdgcn_fmed3f(v, -lim, lim); }
 
@@ -102,18 +59,7 @@ __global__ __launch_bounds__(256, 2) void signw_tiled(Args a) {
   unsigned long long wn[KP][CB], wcur[KP][CB];
   auto load = [&](int st) {
     const int f = st * 64 + sf;
-#pragma unroll
-    for (int i = 0; i < kRows; ++i) {
-      const long long mi = m0 + sr + 16 * i;
-      const float* p = a.x + (mi < a.M ? mi : a.M - 1) * a.F;
-      if constexpr (VEC) {
-        const float4 v = *reinterpret_cast<const float4*>(p + min(f, a.F - 4));
-        xr[i][0] = v.x; xr[i][1] = v.y; xr[i][2] = v.z; xr[i][3] = v.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xr[i][j] = p[min(f + j, a.F - 1)];
-      }
-    }
+    load_rows4<VEC>(a.x, m0 + sr, a.M, a.F, f, xr);
 #pragma unroll
     for (int q = 0; q < KP; ++q)
 #pragma unroll
@@ -129,12 +75,7 @@ __global__ __launch_bounds__(256, 2) void signw_tiled(Args a) {
       float c[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) c[j] = f + j < a.F ? clampv(xr[i][j], a.lim) : 0.f;
-      unsigned h0, l0, h1, l1;
-      split_pair(c[0], c[1], h0, l0);
-      split_pair(c[2], c[3], h1, l1);
-      unsigned char* d = s_x + (sr + 16 * i) * kPitch + sf * 2;
-      *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(d + BM * kPitch) = make_uint2(l0, l1);
+      stash_hi_lo(s_x + (sr + 16 * i) * kPitch + sf * 2, BM * kPitch, c);
     }
   };
 
@@ -158,37 +99,7 @@ __global__ __launch_bounds__(256, 2) void signw_tiled(Args a) {
       for (int cb = 0; cb < CB; ++cb) wcur[q][cb] = wn[q][cb];
     __syncthreads();
     if (st + 1 < a.nw) load(st + 1);                  // in flight during the MFMAs below
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      Frag ah[RB], al[RB], bw[KP][CB];
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb) {
-        const unsigned char* r = s_x + (wr * 32 * RB + rb * 32 + col) * kPitch + 32 * s + 16 * hh;
-        const uint4 vh = *reinterpret_cast<const uint4*>(r);
-        const uint4 vl = *reinterpret_cast<const uint4*>(r + BM * kPitch);
-        ah[rb].u[0] = vh.x; ah[rb].u[1] = vh.y; ah[rb].u[2] = vh.z; ah[rb].u[3] = vh.w;
-        al[rb].u[0] = vl.x; al[rb].u[1] = vl.y; al[rb].u[2] = vl.z; al[rb].u[3] = vl.w;
-      }
-#pragma unroll
-      for (int q = 0; q < KP; ++q)
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) bw[q][cb] = expand8((unsigned)(wcur[q][cb] >> (16 * s + 8 * hh)));
-      // hi products of every tile first, then lo: dependent MFMAs on one accumulator are KP * RB * CB apart
-#pragma unroll
-      for (int q = 0; q < KP; ++q)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-          for (int cb = 0; cb < CB; ++cb)
-            acc[q][rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rb].v, bw[q][cb].v, acc[q][rb][cb], 0, 0, 0);
-#pragma unroll
-      for (int q = 0; q < KP; ++q)
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-          for (int cb = 0; cb < CB; ++cb)
-            acc[q][rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rb].v, bw[q][cb].v, acc[q][rb][cb], 0, 0, 0);
-    }
+    mma_stage(s_x, BM * kPitch, wr * 32 * RB, col, hh, wcur, acc);
   }
 
 #pragma unroll
@@ -203,7 +114,7 @@ __global__ __launch_bounds__(256, 2) void signw_tiled(Args a) {
     for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const long long m = m0 + wr * 32 * RB + rb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        const long long m = d_row(m0 + wr * 32 * RB + rb * 32, i, hh);
         if (m >= a.M) continue;
         float* yp = a.y + m * a.O + o;
         float v = a.accumulate ? *yp : b;
@@ -218,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void signw_tiled(Args a) {
 // ---------------------------------------------------------------------------------------------------------------------
 template <int KP, bool VEC>
 __global__ __launch_bounds__(64 * kSplitWaves) void signw_split(Args a) {
-  __shared__ float s_red[kSplitWaves][KP][16][64];    // every wave's partial sums, [register][lane]
+  __shared__ float s_red[kSplitWaves][KP][16][64];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int col = lane & 31, hh = lane >> 5;
   const int o0 = blockIdx.x * 32;
@@ -282,11 +193,7 @@ __global__ __launch_bounds__(64 * kSplitWaves) void signw_split(Args a) {
     }
   }
 
-#pragma unroll
-  for (int q = 0; q < KP; ++q)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s_red[wid][q][i][lane] = acc[q][i];
-  __syncthreads();
+  split_reduce(s_red, acc, wid, lane);
 
   // wave g finishes registers 2 g and 2 g + 1 of the tile: the partial sums added in wave order, then the epilogue
   const int o = o0 + col;
@@ -298,37 +205,26 @@ __global__ __launch_bounds__(64 * kSplitWaves) void signw_split(Args a) {
 #pragma unroll
   for (int ii = 0; ii < 2; ++ii) {
     const int i = 2 * wid + ii;
-    const long long m = m0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+    const long long m = m0 + (i & 3) + 8 * (i >> 2) + 4 * hh;       // d_row of lsq_signw_mma.h, written out (see there)
     if (m >= a.M) continue;
     float* yp = a.y + m * a.O + o;
     float v = a.accumulate ? *yp : b;
 #pragma unroll
-    for (int q = 0; q < KP; ++q) {
-      float sum = s_red[0][q][i][lane];
-#pragma unroll
-      for (int w = 1; w < kSplitWaves; ++w) sum += s_red[w][q][i][lane];
-      v = fmaf(sum, ws[q], v);
-    }
+    for (int q = 0; q < KP; ++q) v = fmaf(split_sum(s_red, q, i, lane), ws[q], v);
     *yp = v;
   }
 }
 
 template <int KP>
-int launch(const Args& a, bool split, bool big, bool vec, hipStream_t st) {
-  if (split) {
-    const dim3 grid((unsigned)((a.O + 31) / 32), (unsigned)((a.M + 31) / 32));
-    if (vec) hipLaunchKernelGGL((signw_split<KP, true>), grid, dim3(64 * kSplitWaves), 0, st, a);
-    else hipLaunchKernelGGL((signw_split<KP, false>), grid, dim3(64 * kSplitWaves), 0, st, a);
-  } else if (big) {
-    const dim3 grid((unsigned)((a.M + 127) / 128), (unsigned)((a.O + 127) / 128));
-    if (vec) hipLaunchKernelGGL((signw_tiled<KP, 2, 2, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((signw_tiled<KP, 2, 2, false>), grid, dim3(256), 0, st, a);
-  } else {
-    const dim3 grid((unsigned)((a.M + 63) / 64), (unsigned)((a.O + 63) / 64));
-    if (vec) hipLaunchKernelGGL((signw_tiled<KP, 1, 1, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((signw_tiled<KP, 1, 1, false>), grid, dim3(256), 0, st, a);
-  }
-  return (int)hipGetLastError();
+int launch(const Args& a, TileRule rule, bool vec, hipStream_t st) {
+  const TileKernels<Args> k = {{signw_split<KP, false>, signw_split<KP, true>},
+                               {signw_tiled<KP, 2, 2, false>, signw_tiled<KP, 2, 2, true>},
+                               {signw_tiled<KP, 1, 1, false>, signw_tiled<KP, 1, 1, true>}};
+  auto grid = [&](int t) {                            // split: x = columns, y = rows; tiled: x = rows, y = columns
+    const unsigned rows = (unsigned)((a.M + t - 1) / t), cols = (unsigned)((a.O + t - 1) / t);
+    return t == 32 ? dim3(cols, rows) : dim3(rows, cols);
+  };
+  return launch_tiles(k, a, rule, vec, grid, st);
 }
 
 }  // namespace
@@ -355,16 +251,13 @@ extern "C" int lsq_linear_signw(const float* x, float clamp_alpha, const uint64_
   a.lim = clamp_alpha >= 0.f ? clamp_alpha : INFINITY;
   // 16-byte activation loads where every row starts on 16 bytes (same values, same bits as the 4-byte loads)
   const bool vec = ((uintptr_t)x & 15) == 0 && F % 4 == 0;
-  // fewer 64 x 64 tiles than CUs: the weight stream bounds the call, so the F of each 32 x 32 tile is split over 8 waves;
-  // 128 x 128 tiles where there are at least 256 of them (one per CU), 64 x 64 otherwise
-  const bool split = ((M + 63) / 64) * ((O + 63) / 64) < 256;
-  const bool big = ((M + 127) / 128) * ((O + 127) / 128) >= 256;
+  const TileRule rule = tile_rule(M, O);
   hipStream_t st = (hipStream_t)stream;
   for (int q0 = 0; q0 < kw_planes; q0 += 2) {         // planes in pairs: two accumulators share every A fragment
     a.wbits = (const unsigned long long*)wbits + (long long)q0 * a.wplane;
     a.wscales = wscales + (long long)q0 * O;
     a.accumulate = q0 ? 1 : 0;
-    const int e = kw_planes - q0 >= 2 ? launch<2>(a, split, big, vec, st) : launch<1>(a, split, big, vec, st);
+    const int e = kw_planes - q0 >= 2 ? launch<2>(a, rule, vec, st) : launch<1>(a, rule, vec, st);
     if (e) return e;
   }
   return LSQ_OK;

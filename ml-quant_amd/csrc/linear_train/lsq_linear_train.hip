@@ -2,23 +2,21 @@
 // cores of gfx950 (v_mfma_f32_32x32x16_bf16) -- the input gradient of QuantLinear, lsq_linear_signw transposed.
 //
 // As a GEMM:  gx[m][f] = sum_q sum_o (gy[m][o] ws[q][o]) s_q[o][f],  M = rows, K = O output features (per plane), N = F.
-// Gradient rows are operand A (rows m), weights operand B (columns f): a lane of D holds ONE column f (lane & 31) and 16
-// rows, so a store instruction writes 32 consecutive floats of a row of gx per half-wave.  Lane (r = lane & 31,
-// h = lane >> 5) holds A[row r][k = 8 h + j] and B[k = 8 h + j][col r] in element j = 0..7 of its fragments.
+// Gradient rows are operand A (rows m), weights operand B (columns f); fragment layout, the hi / lo split and the sign-bit
+// expansion: csrc/linear/lsq_signw_mma.h.
 //   * WEIGHT: the forward's planes hold the bits of 64 FEATURES in a word; here k runs over o, so a first kernel
 //     (transpose_planes) writes the transposed image T[q][ceil(O / 64)][ceil16(F)] into the caller's workspace: one wave
 //     per 64 x 64 bit block, lane j reads the word of output feature 64 w + j, ballot i collects bit i of all lanes =
-//     the word of input feature i.  After it a lane's B fragment is 8 consecutive bits of one word of its column and
-//     becomes 8 bf16 +-1.0 in registers (expand8, as the forward): one bit per weight in memory throughout.
+//     the word of input feature i.  After it a lane's B fragment is 8 consecutive bits of one word of its column, as in
+//     the forward: one bit per weight in memory throughout.
 //   * GRADIENT: a = fl32(gy ws[q][o]) -- the scale is per (plane, k) here, so it goes into A and all planes add into ONE
-//     accumulator --, split into hi = bf16(a) and lo = bf16(a - hi); two MFMAs per k-step (hi, then lo).  Output features
-//     past O are staged as 0: the padded slots of a plane are zero words and would read as -1.
+//     accumulator --, then split.  Output features past O are staged as 0: the padded slots of a plane are zero words and
+//     would read as -1.
 //   * Rows past M and columns past F read a valid row / column and are never stored.
 // Two kernels behind the one entry point (selected from M and F, see lsq_linear_signw_dgrad):
 //   dgrad_tiled  M x F tiles of 128 x 128 or 64 x 64, four waves (2 x 2), over the kw * ceil(O / 64) stages (plane-major);
-//                per stage the workgroup scales and splits its rows' gradients ONCE into LDS (hi and lo rows of 144 bytes:
-//                16-byte pad, conflict-free ds_read_b128 fragments); the next stage's gradients, scales and weight words
-//                are loaded into registers while the MFMAs of this one run.
+//                per stage the workgroup scales and splits its rows' gradients ONCE into LDS; the next stage's gradients,
+//                scales and weight words are loaded into registers while the MFMAs of this one run.
 //   dgrad_split  few tiles (LeNet fc1, the ResNet head): one 32 x 32 tile of gx per workgroup, the stages split over 8
 //                waves, each reading, scaling, splitting and multiplying its own range straight from global memory; the
 //                partial sums meet in LDS and are added in wave order.
@@ -28,19 +26,9 @@
 #include <stdint.h>
 
 #include "lsq_hip_linear_train.h"
+#include "../linear/lsq_signw_mma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) unsigned short u16x2;
-
-union Frag {
-  unsigned u[4];
-  bf16x8 v;
-};
 
 struct Args {
   const float* gy;                    // [M][O]
@@ -50,35 +38,6 @@ struct Args {
   long long M;
   int F, O, fpad, nwo, stages;        // fpad = ceil16(F); nwo = ceil(O / 64); stages = kw * nwo
 };
-
-constexpr int kPitch = 144;           // LDS bytes per staged row of dgrad_tiled: 64 bf16 + 16 bytes of pad
-constexpr int kSplitWaves = 8;        // waves of dgrad_split, one range of stages each
-
-// v = hi + lo in bf16: hi = bf16(v) (round to nearest even), lo = bf16(v - hi); v - hi is exact in fp32, so
-// |v - hi - lo| <= 2^-8 |v - hi| <= 2^-16 |v|
-__device__ __forceinline__ void split_pair(float v0, float v1, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {v0, v1};
-  const bf16x2 h = __builtin_convertvector(v, bf16x2);
-  const f32x2 r = v - __builtin_convertvector(h, f32x2);
-  const bf16x2 l = __builtin_convertvector(r, bf16x2);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-
-// 8 sign bits (bit j set = +1) -> B fragment: element j = +-1.0 in bf16, half (j & 1) of dword j >> 1.  The inverted bits
-// in both 16-bit halves, one packed shift brings bit 2d / 2d + 1 to the sign position of the low / high half.
-__device__ __forceinline__ Frag expand8(unsigned bits) {
-  const unsigned short m = (unsigned short)(~bits & 0xFFu);
-  const u16x2 rep = {m, m};
-  Frag f;
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const u16x2 sh = {(unsigned short)(15 - 2 * d), (unsigned short)(14 - 2 * d)};
-    const u16x2 s = rep << sh;
-    f.u[d] = (__builtin_bit_cast(unsigned, s) & 0x80008000u) | 0x3F803F80u;
-  }
-  return f;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // T[q][w][f] bit j = wbits[q][f / 64][64 w + j] bit f % 64: one wave per 64 x 64 bit block (grid-stride over the blocks).
@@ -120,28 +79,17 @@ __global__ __launch_bounds__(256, 2) void dgrad_tiled(Args a) {
   const int sf = (tid & 15) * 4, sr = tid >> 4;       // staging role: output features sf .. sf + 3 of rows sr + 16 i
 
   float gr[kRows][4], sc[4];
-  unsigned long long wn[CB], wcur[CB];
+  unsigned long long wn[1][CB], wcur[1][CB];      // [1]: one accumulator set for all planes (mma_stage<NQ = 1>)
   auto load = [&](int it) {
     const int q = it / a.nwo, st = it - q * a.nwo;
     const int o = st * 64 + sf;
-#pragma unroll
-    for (int i = 0; i < kRows; ++i) {
-      const long long mi = m0 + sr + 16 * i;
-      const float* p = a.gy + (mi < a.M ? mi : a.M - 1) * a.O;
-      if constexpr (VEC) {
-        const float4 v = *reinterpret_cast<const float4*>(p + min(o, a.O - 4));
-        gr[i][0] = v.x; gr[i][1] = v.y; gr[i][2] = v.z; gr[i][3] = v.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gr[i][j] = p[min(o + j, a.O - 1)];
-      }
-    }
+    load_rows4<VEC>(a.gy, m0 + sr, a.M, a.O, o, gr);
 #pragma unroll
     for (int j = 0; j < 4; ++j) sc[j] = a.wscales[(long long)q * a.O + min(o + j, a.O - 1)];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {
       const int f = min(f0 + wc * 32 * CB + cb * 32 + col, a.fpad - 1);
-      wn[cb] = a.tbits[(long long)it * a.fpad + f];
+      wn[0][cb] = a.tbits[(long long)it * a.fpad + f];
     }
   };
   auto stash = [&](int it) {
@@ -152,56 +100,27 @@ __global__ __launch_bounds__(256, 2) void dgrad_tiled(Args a) {
       float c[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) c[j] = o + j < a.O ? __fmul_rn(gr[i][j], sc[j]) : 0.f;
-      unsigned h0, l0, h1, l1;
-      split_pair(c[0], c[1], h0, l0);
-      split_pair(c[2], c[3], h1, l1);
-      unsigned char* d = s_a + (sr + 16 * i) * kPitch + sf * 2;
-      *reinterpret_cast<uint2*>(d) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(d + BM * kPitch) = make_uint2(l0, l1);
+      stash_hi_lo(s_a + (sr + 16 * i) * kPitch + sf * 2, BM * kPitch, c);
     }
   };
 
-  f32x16 acc[RB][CB];
+  f32x16 acc[1][RB][CB];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[rb][cb][i] = 0.f;
+      for (int i = 0; i < 16; ++i) acc[0][rb][cb][i] = 0.f;
 
   load(0);
   for (int it = 0; it < a.stages; ++it) {
     __syncthreads();                                  // every wave is done reading the previous stage
     stash(it);
 #pragma unroll
-    for (int cb = 0; cb < CB; ++cb) wcur[cb] = wn[cb];
+    for (int cb = 0; cb < CB; ++cb) wcur[0][cb] = wn[0][cb];
     __syncthreads();
     if (it + 1 < a.stages) load(it + 1);              // in flight during the MFMAs below
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      Frag ah[RB], al[RB], bw[CB];
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb) {
-        const unsigned char* r = s_a + (wr * 32 * RB + rb * 32 + col) * kPitch + 32 * s + 16 * hh;
-        const uint4 vh = *reinterpret_cast<const uint4*>(r);
-        const uint4 vl = *reinterpret_cast<const uint4*>(r + BM * kPitch);
-        ah[rb].u[0] = vh.x; ah[rb].u[1] = vh.y; ah[rb].u[2] = vh.z; ah[rb].u[3] = vh.w;
-        al[rb].u[0] = vl.x; al[rb].u[1] = vl.y; al[rb].u[2] = vl.z; al[rb].u[3] = vl.w;
-      }
-#pragma unroll
-      for (int cb = 0; cb < CB; ++cb) bw[cb] = expand8((unsigned)(wcur[cb] >> (16 * s + 8 * hh)));
-      // hi products of every tile first, then lo: dependent MFMAs on one accumulator are RB * CB apart
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-          acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rb].v, bw[cb].v, acc[rb][cb], 0, 0, 0);
-#pragma unroll
-      for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-          acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rb].v, bw[cb].v, acc[rb][cb], 0, 0, 0);
-    }
+    mma_stage(s_a, BM * kPitch, wr * 32 * RB, col, hh, wcur, acc);
   }
 
 #pragma unroll
@@ -212,9 +131,9 @@ __global__ __launch_bounds__(256, 2) void dgrad_tiled(Args a) {
     for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const long long m = m0 + wr * 32 * RB + rb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        const long long m = d_row(m0 + wr * 32 * RB + rb * 32, i, hh);
         if (m >= a.M) continue;
-        a.gx[m * a.F + f] = acc[rb][cb][i];
+        a.gx[m * a.F + f] = acc[0][rb][cb][i];
       }
     }
   }
@@ -223,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void dgrad_tiled(Args a) {
 // ---------------------------------------------------------------------------------------------------------------------
 template <bool VEC>
 __global__ __launch_bounds__(64 * kSplitWaves) void dgrad_split(Args a) {
-  __shared__ float s_red[kSplitWaves][16][64];        // every wave's partial sums, [register][lane]
+  __shared__ float s_red[kSplitWaves][1][16][64];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int col = lane & 31, hh = lane >> 5;
   const int f0 = blockIdx.x * 32;
@@ -234,9 +153,9 @@ __global__ __launch_bounds__(64 * kSplitWaves) void dgrad_split(Args a) {
   const float* grow = a.gy + mr * a.O;
   const int fw = min(f0 + col, a.fpad - 1);                      // the lane's B column
 
-  f32x16 acc;
+  f32x16 acc[1];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  for (int i = 0; i < 16; ++i) acc[0][i] = 0.f;
 
   float gn[32], sn[32];
   unsigned long long wn;
@@ -279,14 +198,12 @@ __global__ __launch_bounds__(64 * kSplitWaves) void dgrad_split(Args a) {
 #pragma unroll
       for (int d = 0; d < 4; ++d) split_pair(c[2 * d], c[2 * d + 1], hi.u[d], lo.u[d]);
       const Frag bw = expand8((unsigned)(wv >> (16 * s + 8 * hh)));
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hi.v, bw.v, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lo.v, bw.v, acc, 0, 0, 0);
+      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hi.v, bw.v, acc[0], 0, 0, 0);
+      acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lo.v, bw.v, acc[0], 0, 0, 0);
     }
   }
 
-#pragma unroll
-  for (int i = 0; i < 16; ++i) s_red[wid][i][lane] = acc[i];
-  __syncthreads();
+  split_reduce(s_red, acc, wid, lane);
 
   // wave g finishes registers 2 g and 2 g + 1 of the tile: the partial sums added in wave order
   const int f = f0 + col;
@@ -294,30 +211,21 @@ __global__ __launch_bounds__(64 * kSplitWaves) void dgrad_split(Args a) {
 #pragma unroll
   for (int ii = 0; ii < 2; ++ii) {
     const int i = 2 * wid + ii;
-    const long long m = m0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+    const long long m = m0 + (i & 3) + 8 * (i >> 2) + 4 * hh;       // d_row of lsq_signw_mma.h, written out (see there)
     if (m >= a.M) continue;
-    float sum = s_red[0][i][lane];
-#pragma unroll
-    for (int w = 1; w < kSplitWaves; ++w) sum += s_red[w][i][lane];
-    a.gx[m * a.F + f] = sum;
+    a.gx[m * a.F + f] = split_sum(s_red, 0, i, lane);
   }
 }
 
-int launch(const Args& a, bool split, bool big, bool vec, hipStream_t st) {
-  if (split) {
-    const dim3 grid((unsigned)((a.F + 31) / 32), (unsigned)((a.M + 31) / 32));
-    if (vec) hipLaunchKernelGGL((dgrad_split<true>), grid, dim3(64 * kSplitWaves), 0, st, a);
-    else hipLaunchKernelGGL((dgrad_split<false>), grid, dim3(64 * kSplitWaves), 0, st, a);
-  } else if (big) {
-    const dim3 grid((unsigned)((a.M + 127) / 128), (unsigned)((a.F + 127) / 128));
-    if (vec) hipLaunchKernelGGL((dgrad_tiled<2, 2, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((dgrad_tiled<2, 2, false>), grid, dim3(256), 0, st, a);
-  } else {
-    const dim3 grid((unsigned)((a.M + 63) / 64), (unsigned)((a.F + 63) / 64));
-    if (vec) hipLaunchKernelGGL((dgrad_tiled<1, 1, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((dgrad_tiled<1, 1, false>), grid, dim3(256), 0, st, a);
-  }
-  return (int)hipGetLastError();
+int launch(const Args& a, TileRule rule, bool vec, hipStream_t st) {
+  const TileKernels<Args> k = {{dgrad_split<false>, dgrad_split<true>},
+                               {dgrad_tiled<2, 2, false>, dgrad_tiled<2, 2, true>},
+                               {dgrad_tiled<1, 1, false>, dgrad_tiled<1, 1, true>}};
+  auto grid = [&](int t) {                            // split: x = columns, y = rows; tiled: x = rows, y = columns
+    const unsigned rows = (unsigned)((a.M + t - 1) / t), cols = (unsigned)((a.F + t - 1) / t);
+    return t == 32 ? dim3(cols, rows) : dim3(rows, cols);
+  };
+  return launch_tiles(k, a, rule, vec, grid, st);
 }
 
 bool in_limits(int kw_planes, int64_t F, int64_t O) {
@@ -365,9 +273,5 @@ extern "C" int lsq_linear_signw_dgrad(const float* gy, const uint64_t* wbits, in
 
   // 16-byte gradient loads where every row starts on 16 bytes (same values, same bits as the 4-byte loads)
   const bool vec = ((uintptr_t)gy & 15) == 0 && O % 4 == 0;
-  // the tile rule of lsq_linear_signw with F in the place of O: fewer 64 x 64 tiles than CUs -> the summed dimension of
-  // each 32 x 32 tile split over 8 waves; 128 x 128 tiles where there are at least 256 of them, 64 x 64 otherwise
-  const bool split = ((M + 63) / 64) * ((F + 63) / 64) < 256;
-  const bool big = ((M + 127) / 128) * ((F + 127) / 128) >= 256;
-  return launch(a, split, big, vec, st);
+  return launch(a, tile_rule(M, F), vec, st);
 }

@@ -3,27 +3,24 @@
 // activations.
 //
 // As a GEMM:  gwq[o][f] = sum_p sum_m (gy[m][o] xs[p][m / T]) b_p[m][f],  D rows = O output features, K = M rows (per
-// plane), D columns = F input features.  A lane of D holds ONE column f (lane & 31) and 16 rows o, so a store instruction
-// writes 32 consecutive floats of a row of gwq per half-wave.  Lane (r = lane & 31, h = lane >> 5) holds A[row r][k = 8 h + j]
-// and B[k = 8 h + j][col r] in element j = 0..7 of its fragments.
+// plane), D columns = F input features; fragment layout, the hi / lo split and the sign-bit expansion:
+// csrc/linear/lsq_signw_mma.h.
 //   * INPUT: a first kernel (sign_image) walks x row-major and writes X[p][ceil(M / 64)][ceil16(F)]: bit j of word
 //     [p][w][f] = the chain's sign b_p at row 64 w + j, feature f.  A lane owns one feature and ORs the bits of 64 rows into
 //     its kx words -- the layout the GEMM wants is the natural one, no ballot, no LDS.  After it a lane's B fragment is 8
-//     consecutive bits of one word of its column and becomes 8 bf16 +-1.0 in registers (expand8).
+//     consecutive bits of one word of its column.
 //   * GRADIENT: a = fl32(gy xs[p][m / T]) -- the scale is per (plane, k), so it goes into A and all planes add into ONE
-//     accumulator --, split into hi = bf16(a) and lo = bf16(a - hi); two MFMAs per k-step (hi, then lo).  The A fragment is 8
-//     consecutive m of one o while gy is contiguous in o: the tile goes through LDS transposed.  Rows past M are staged as
-//     0 (their image bits are 0 and would read as -1).
+//     accumulator --, then split.  The A fragment is 8 consecutive m of one o while gy is contiguous in o: the tile goes
+//     through LDS transposed.  Rows past M are staged as 0 (their image bits are 0 and would read as -1).
 //   * Output features past O and columns past F read a valid row / column and are never stored.
 // Three kernels behind the one entry point (selected from O and F, see lsq_linear_signx_wgrad):
 //   sign_image   one wave per 64 rows x 64 features.
 //   wgrad_tiled  O x F tiles of 128 x 128 or 64 x 64, four waves (2 x 2), over ceil(M / 64) * kx stages (word-major, the
 //                planes of a word inside it: the gradient rows of a word are loaded ONCE for all planes); per stage the
-//                workgroup scales and splits its gradient tile into LDS, o-major (hi and lo rows of 144 bytes: 16-byte
-//                pad, conflict-free ds_read_b128 fragments).  A staging thread holds rows m, m + 1 of four output features and
-//                stores four packed bf16 pairs; the lanes of a half-wave are 2 groups of four output features x 16 row
-//                pairs, which puts the 32 stores of an instruction on 32 different banks.  The next stage's gradients,
-//                scales and image words are loaded into registers while the MFMAs of this one run.
+//                workgroup scales and splits its gradient tile into LDS, o-major.  A staging thread holds rows m, m + 1 of
+//                four output features and stores four packed bf16 pairs; the lanes of a half-wave are 2 groups of four
+//                output features x 16 row pairs, which puts the 32 stores of an instruction on 32 different banks.  The
+//                next stage's gradients, scales and image words are loaded into registers while the MFMAs of this one run.
 //   wgrad_split  few tiles (LeNet fc1, the ResNet head): one 32 x 32 tile of gwq per workgroup, the (word, plane, 16-row
 //                step) units split over 8 waves, each reading, scaling, splitting and multiplying its own range straight from
 //                global memory; the partial sums meet in LDS and are added in wave order.
@@ -33,19 +30,9 @@
 #include <stdint.h>
 
 #include "lsq_hip_linear_wgrad.h"
+#include "../linear/lsq_signw_mma.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) unsigned short u16x2;
-
-union Frag {
-  unsigned u[4];
-  bf16x8 v;
-};
 
 struct Args {
   const float* gy;                    // [M][O]
@@ -55,35 +42,6 @@ struct Args {
   int M, N, T, F, O, kx, fpad, nwm;   // fpad = ceil16(F); nwm = ceil(M / 64)
   int ntf;                            // wgrad_split: tiles of 32 columns
 };
-
-constexpr int kPitch = 144;           // LDS bytes per staged row of wgrad_tiled: 64 bf16 + 16 bytes of pad
-constexpr int kSplitWaves = 8;        // waves of wgrad_split, one range of units each
-
-// v = hi + lo in bf16: hi = bf16(v) (round to nearest even), lo = bf16(v - hi); v - hi is exact in fp32, so
-// |v - hi - lo| <= 2^-8 |v - hi| <= 2^-16 |v|
-__device__ __forceinline__ void split_pair(float v0, float v1, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {v0, v1};
-  const bf16x2 h = __builtin_convertvector(v, bf16x2);
-  const f32x2 r = v - __builtin_convertvector(h, f32x2);
-  const bf16x2 l = __builtin_convertvector(r, bf16x2);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-
-// 8 sign bits (bit j set = +1) -> B fragment: element j = +-1.0 in bf16, half (j & 1) of dword j >> 1.  The inverted bits
-// in both 16-bit halves, one packed shift brings bit 2d / 2d + 1 to the sign position of the low / high half.
-__device__ __forceinline__ Frag expand8(unsigned bits) {
-  const unsigned short m = (unsigned short)(~bits & 0xFFu);
-  const u16x2 rep = {m, m};
-  Frag f;
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    const u16x2 sh = {(unsigned short)(15 - 2 * d), (unsigned short)(14 - 2 * d)};
-    const u16x2 s = rep << sh;
-    f.u[d] = (__builtin_bit_cast(unsigned, s) & 0x80008000u) | 0x3F803F80u;
-  }
-  return f;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // X[p][w][f] bit j = [d_p >= 0] of the quantizer chain at row 64 w + j, feature f (lsq_ste.hip: ste_one): one wave per
@@ -157,7 +115,7 @@ __global__ __launch_bounds__(256, (RB == 2 && !VEC) ? 1 : 2) void wgrad_tiled(Ar
   const int sq = ((lane & 1) + 2 * hh) * 4, sp = (lane >> 1) & 15;
 
   float gr[kPass][2][4], sc[kPass][2];
-  unsigned long long wn[CB], wcur[CB];
+  unsigned long long wn[1][CB], wcur[1][CB];      // [1]: one accumulator set for all planes (mma_stage<NQ = 1>)
   auto load_g = [&](int w) {
 #pragma unroll
     for (int i = 0; i < kPass; ++i) {
@@ -191,7 +149,7 @@ __global__ __launch_bounds__(256, (RB == 2 && !VEC) ? 1 : 2) void wgrad_tiled(Ar
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {
       const int f = min(f0 + wc * 32 * CB + cb * 32 + col, a.fpad - 1);
-      wn[cb] = a.img[((long long)p * a.nwm + w) * a.fpad + f];
+      wn[0][cb] = a.img[((long long)p * a.nwm + w) * a.fpad + f];
     }
   };
   auto stash = [&](int w) {
@@ -214,13 +172,13 @@ __global__ __launch_bounds__(256, (RB == 2 && !VEC) ? 1 : 2) void wgrad_tiled(Ar
     }
   };
 
-  f32x16 acc[RB][CB];
+  f32x16 acc[1][RB][CB];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) acc[rb][cb][i] = 0.f;
+      for (int i = 0; i < 16; ++i) acc[0][rb][cb][i] = 0.f;
 
   load_g(0);
   load_sw(0, 0);
@@ -229,7 +187,7 @@ __global__ __launch_bounds__(256, (RB == 2 && !VEC) ? 1 : 2) void wgrad_tiled(Ar
       __syncthreads();                                // every wave is done reading the previous stage
       stash(w);
 #pragma unroll
-      for (int cb = 0; cb < CB; ++cb) wcur[cb] = wn[cb];
+      for (int cb = 0; cb < CB; ++cb) wcur[0][cb] = wn[0][cb];
       __syncthreads();
       if (p + 1 < a.kx) {                             // in flight during the MFMAs below
         load_sw(w, p + 1);
@@ -237,31 +195,7 @@ __global__ __launch_bounds__(256, (RB == 2 && !VEC) ? 1 : 2) void wgrad_tiled(Ar
         load_g(w + 1);
         load_sw(w + 1, 0);
       }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        Frag ah[RB], al[RB], bw[CB];
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-          const unsigned char* r = s_a + (wr * 32 * RB + rb * 32 + col) * kPitch + 32 * s + 16 * hh;
-          const uint4 vh = *reinterpret_cast<const uint4*>(r);
-          const uint4 vl = *reinterpret_cast<const uint4*>(r + BO * kPitch);
-          ah[rb].u[0] = vh.x; ah[rb].u[1] = vh.y; ah[rb].u[2] = vh.z; ah[rb].u[3] = vh.w;
-          al[rb].u[0] = vl.x; al[rb].u[1] = vl.y; al[rb].u[2] = vl.z; al[rb].u[3] = vl.w;
-        }
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) bw[cb] = expand8((unsigned)(wcur[cb] >> (16 * s + 8 * hh)));
-        // hi products of every tile first, then lo: dependent MFMAs on one accumulator are RB * CB apart
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-          for (int cb = 0; cb < CB; ++cb)
-            acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[rb].v, bw[cb].v, acc[rb][cb], 0, 0, 0);
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-          for (int cb = 0; cb < CB; ++cb)
-            acc[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rb].v, bw[cb].v, acc[rb][cb], 0, 0, 0);
-      }
+      mma_stage(s_a, BO * kPitch, wr * 32 * RB, col, hh, wcur, acc);
     }
   }
 
@@ -273,9 +207,9 @@ __global__ __launch_bounds__(256, (RB == 2 && !VEC) ? 1 : 2) void wgrad_tiled(Ar
     for (int rb = 0; rb < RB; ++rb) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int o = o0 + wr * 32 * RB + rb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        const int o = d_row(o0 + wr * 32 * RB + rb * 32, i, hh);
         if (o >= a.O) continue;
-        a.gwq[(long long)o * a.F + f] = acc[rb][cb][i];
+        a.gwq[(long long)o * a.F + f] = acc[0][rb][cb][i];
       }
     }
   }
@@ -283,7 +217,7 @@ __global__ __launch_bounds__(256, (RB == 2 && !VEC) ? 1 : 2) void wgrad_tiled(Ar
 
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * kSplitWaves) void wgrad_split(Args a) {
-  __shared__ float s_red[kSplitWaves][16][64];        // every wave's partial sums, [register][lane]
+  __shared__ float s_red[kSplitWaves][1][16][64];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int col = lane & 31, hh = lane >> 5;
   const int f0 = ((int)blockIdx.x % a.ntf) * 32;
@@ -295,9 +229,9 @@ __global__ __launch_bounds__(64 * kSplitWaves) void wgrad_split(Args a) {
   const int fl = min(f0 + col, a.fpad - 1);           // the lane's B column
   const unsigned char* bytes = reinterpret_cast<const unsigned char*>(a.img);
 
-  f32x16 acc;
+  f32x16 acc[1];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  for (int i = 0; i < 16; ++i) acc[0][i] = 0.f;
 
   float gn[8], sn[8];
   unsigned bn = 0;
@@ -340,13 +274,11 @@ __global__ __launch_bounds__(64 * kSplitWaves) void wgrad_split(Args a) {
     Frag hi, lo;
 #pragma unroll
     for (int d = 0; d < 4; ++d) split_pair(c[2 * d], c[2 * d + 1], hi.u[d], lo.u[d]);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hi.v, bw.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lo.v, bw.v, acc, 0, 0, 0);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hi.v, bw.v, acc[0], 0, 0, 0);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lo.v, bw.v, acc[0], 0, 0, 0);
   }
 
-#pragma unroll
-  for (int i = 0; i < 16; ++i) s_red[wid][i][lane] = acc[i];
-  __syncthreads();
+  split_reduce(s_red, acc, wid, lane);
 
   // wave g finishes registers 2 g and 2 g + 1 of the tile: the partial sums added in wave order
   const int f = f0 + col;
@@ -354,29 +286,21 @@ __global__ __launch_bounds__(64 * kSplitWaves) void wgrad_split(Args a) {
 #pragma unroll
   for (int ii = 0; ii < 2; ++ii) {
     const int i = 2 * wid + ii;
-    const int o = o0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+    const int o = o0 + (i & 3) + 8 * (i >> 2) + 4 * hh;       // d_row of lsq_signw_mma.h, written out (see there)
     if (o >= a.O) continue;
-    float sum = s_red[0][i][lane];
-#pragma unroll
-    for (int g = 1; g < kSplitWaves; ++g) sum += s_red[g][i][lane];
-    a.gwq[(long long)o * a.F + f] = sum;
+    a.gwq[(long long)o * a.F + f] = split_sum(s_red, 0, i, lane);
   }
 }
 
-int launch(const Args& a, bool split, bool big, bool vec, hipStream_t st) {
-  if (split) {
-    const unsigned tiles = (unsigned)a.ntf * (unsigned)((a.O + 31) / 32);
-    hipLaunchKernelGGL(wgrad_split, dim3(tiles), dim3(64 * kSplitWaves), 0, st, a);
-  } else if (big) {
-    const dim3 grid((unsigned)((a.F + 127) / 128), (unsigned)((a.O + 127) / 128));
-    if (vec) hipLaunchKernelGGL((wgrad_tiled<2, 2, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((wgrad_tiled<2, 2, false>), grid, dim3(256), 0, st, a);
-  } else {
-    const dim3 grid((unsigned)((a.F + 63) / 64), (unsigned)((a.O + 63) / 64));
-    if (vec) hipLaunchKernelGGL((wgrad_tiled<1, 1, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((wgrad_tiled<1, 1, false>), grid, dim3(256), 0, st, a);
-  }
-  return (int)hipGetLastError();
+int launch(const Args& a, TileRule rule, bool vec, hipStream_t st) {
+  const TileKernels<Args> k = {{wgrad_split, wgrad_split},
+                               {wgrad_tiled<2, 2, false>, wgrad_tiled<2, 2, true>},
+                               {wgrad_tiled<1, 1, false>, wgrad_tiled<1, 1, true>}};
+  auto grid = [&](int t) {                            // split: the tiles in x, columns fastest; tiled: x = columns, y = rows
+    const unsigned rows = (unsigned)((a.O + t - 1) / t), cols = (unsigned)((a.F + t - 1) / t);
+    return t == 32 ? dim3((unsigned)a.ntf * rows) : dim3(cols, rows);
+  };
+  return launch_tiles(k, a, rule, vec, grid, st);
 }
 
 bool in_limits(int kx, int64_t N, int64_t T, int64_t F, int64_t O) {
@@ -428,9 +352,5 @@ extern "C" int lsq_linear_signx_wgrad(const float* gy, const float* x, int kx, c
 
   // 16-byte gradient loads where every row starts on 16 bytes (same values, same bits as the 4-byte loads)
   const bool vec = ((uintptr_t)gy & 15) == 0 && O % 4 == 0;
-  // the tile rule of lsq_linear_signw_dgrad with O in the place of M: fewer 64 x 64 tiles than CUs -> the summed dimension
-  // of each 32 x 32 tile split over 8 waves; 128 x 128 tiles where there are at least 256 of them, 64 x 64 otherwise
-  const bool split = ((O + 63) / 64) * ((F + 63) / 64) < 256;
-  const bool big = ((O + 127) / 128) * ((F + 127) / 128) >= 256;
-  return launch(a, split, big, vec, st);
+  return launch(a, tile_rule(O, F), vec, st);
 }

@@ -14,8 +14,9 @@ from typing import Optional, Sequence
 
 import torch
 
-_LIB_PATH = os.environ.get('LSQ_HIP_LIB') or os.path.join(   # (LSQ_HIP_LIB: developer builds, e.g. -DLSQ_PHASE_CLOCKS)
-    os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib', 'liblsq_hip.so')
+_LIB_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib')
+# (LSQ_HIP_LIB: developer builds, e.g. -DLSQ_PHASE_CLOCKS)
+_LIB_PATH = os.environ.get('LSQ_HIP_LIB') or os.path.join(_LIB_DIR, 'liblsq_hip.so')
 _lock = threading.Lock()
 _lib = None
 
@@ -112,21 +113,27 @@ def _declare(lib):
     lib.lsq_stem_conv_pool.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
 
 
+def _load(path, make_dir, declare, version_symbol, version, soname):
+    """Load one of the C-ABI libraries: ``path`` must exist (no fallback: a missing library is an error that says how to
+    build it, ``make -C ml-quant_amd/<make_dir>``), ``declare(handle)`` sets the prototypes, and ``version_symbol()`` must
+    return ``version``.  Loads are serialized; a ``*_lib()`` function keeps the handle in its own module global."""
+    with _lock:
+        if not os.path.exists(path):
+            raise LsqHipError(
+                f'{path} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
+                f'(or `make -C ml-quant_amd/{make_dir}`). The HIP path has no fallback.')
+        handle = ctypes.CDLL(path)
+        declare(handle)
+        if getattr(handle, version_symbol)() != version:
+            raise LsqHipError(f'{soname} ABI version mismatch')
+        return handle
+
+
 def lib():
     """Load (once) and return the C-ABI library; raises if it has not been built."""
     global _lib
     if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(_LIB_PATH):
-                    raise LsqHipError(
-                        f'{_LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
-                        '(or `make -C ml-quant_amd/csrc`). The HIP path has no fallback.')
-                handle = ctypes.CDLL(_LIB_PATH)
-                _declare(handle)
-                if handle.lsq_abi_version() != ABI_VERSION:
-                    raise LsqHipError('liblsq_hip.so ABI version mismatch')
-                _lib = handle
+        _lib = _load(_LIB_PATH, 'csrc', _declare, 'lsq_abi_version', ABI_VERSION, 'liblsq_hip.so')
     return _lib
 
 
@@ -276,19 +283,24 @@ def _ws_bytes(fn: str, rows: int) -> int:
     return need
 
 
-def solver_workspace(rows: int, device) -> torch.Tensor:
-    """Scratch for the LS2/LST solve (slot records passed from the sweep to the solve kernel); cached per
-    device and grown on demand -- kernels of one stream run in order, so sharing it is safe."""
-    need = _ws_bytes('lsq_solver_workspace_bytes', rows)
+def _stream_buffer(cache: dict, need: int, device, zeroed: bool = False) -> torch.Tensor:
+    """The uint8 buffer of at least ``need`` bytes that ``cache`` keeps for (device, its current stream), grown on demand
+    (``zeroed``: a new one starts as zeros) -- kernels of one stream run in order, so sharing it between calls is safe."""
     device = torch.device(device)
     if device.index is None:
         device = torch.device('cuda', torch.cuda.current_device())
     key = (device.index, stream_ptr(device))
-    buf = _ws_cache.get(key)
+    buf = cache.get(key)
     if buf is None or buf.numel() < need:
-        buf = torch.empty((need,), dtype=torch.uint8, device=device)
-        _remember(_ws_cache, key, buf)
+        buf = (torch.zeros if zeroed else torch.empty)((need,), dtype=torch.uint8, device=device)
+        _remember(cache, key, buf)
     return buf
+
+
+def solver_workspace(rows: int, device) -> torch.Tensor:
+    """Scratch for the LS2/LST solve (slot records passed from the sweep to the solve kernel); cached per
+    (device, stream) and grown on demand."""
+    return _stream_buffer(_ws_cache, _ws_bytes('lsq_solver_workspace_bytes', rows), device)
 
 
 _sweep_ws_cache = {}
@@ -296,16 +308,7 @@ _sweep_ws_cache = {}
 def sweep_workspace(rows: int, device) -> torch.Tensor:
     """Row workspace of the ls-1 / gf-k sweeps (partial sums + arrival counters of rows shared by several workgroups):
     any content (the arrival slots carry a per-launch epoch); cached per (device, stream) like the solver's."""
-    need = _ws_bytes('lsq_sweep_workspace_bytes', rows)
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device('cuda', torch.cuda.current_device())
-    key = (device.index, stream_ptr(device))
-    buf = _sweep_ws_cache.get(key)
-    if buf is None or buf.numel() < need:
-        buf = torch.zeros((need,), dtype=torch.uint8, device=device)
-        _remember(_sweep_ws_cache, key, buf)
-    return buf
+    return _stream_buffer(_sweep_ws_cache, _ws_bytes('lsq_sweep_workspace_bytes', rows), device, zeroed=True)
 
 
 _layout_memo = {}
@@ -646,7 +649,7 @@ def ste_backward(x: torch.Tensor, grad_q: torch.Tensor, scales: Optional[torch.T
 
 
 # ---- the training library (include/lsq_hip_train.h): a second shared object, loaded on first use
-_TRAIN_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib', 'liblsq_hip_train.so')
+_TRAIN_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_train.so')
 TRAIN_ABI_VERSION = 1
 _train_lib = None
 
@@ -655,27 +658,22 @@ def train_library_path() -> str:
     return _TRAIN_LIB_PATH
 
 
+def _declare_train(handle):
+    vp, i32, gp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ConvGeom)
+    handle.lsq_train_abi_version.restype = i32
+    handle.lsq_train_abi_version.argtypes = []
+    handle.lsq_train_wgrad_workspace_bytes.restype = ctypes.c_size_t
+    handle.lsq_train_wgrad_workspace_bytes.argtypes = [gp, i32]
+    handle.lsq_train_wgrad.restype = i32
+    handle.lsq_train_wgrad.argtypes = [vp, i32, vp, vp, gp, vp, vp, ctypes.c_size_t, vp]
+
+
 def train_lib():
     """Load (once) and return the training library; raises if it has not been built (no fallback, as ``lib()``)."""
     global _train_lib
     if _train_lib is None:
-        with _lock:
-            if _train_lib is None:
-                if not os.path.exists(_TRAIN_LIB_PATH):
-                    raise LsqHipError(
-                        f'{_TRAIN_LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
-                        '(or `make -C ml-quant_amd/csrc/train`). The HIP path has no fallback.')
-                handle = ctypes.CDLL(_TRAIN_LIB_PATH)
-                vp, i32, gp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ConvGeom)
-                handle.lsq_train_abi_version.restype = i32
-                handle.lsq_train_abi_version.argtypes = []
-                handle.lsq_train_wgrad_workspace_bytes.restype = ctypes.c_size_t
-                handle.lsq_train_wgrad_workspace_bytes.argtypes = [gp, i32]
-                handle.lsq_train_wgrad.restype = i32
-                handle.lsq_train_wgrad.argtypes = [vp, i32, vp, vp, gp, vp, vp, ctypes.c_size_t, vp]
-                if handle.lsq_train_abi_version() != TRAIN_ABI_VERSION:
-                    raise LsqHipError('liblsq_hip_train.so ABI version mismatch')
-                _train_lib = handle
+        _train_lib = _load(_TRAIN_LIB_PATH, 'csrc/train', _declare_train,
+                           'lsq_train_abi_version', TRAIN_ABI_VERSION, 'liblsq_hip_train.so')
     return _train_lib
 
 
@@ -691,13 +689,7 @@ def wgrad(planes: torch.Tensor, kx: int, xscales: torch.Tensor, gy: torch.Tensor
         raise TypeError('activation planes are a contiguous int64 tensor')
     tl = train_lib()
     need = int(tl.lsq_train_wgrad_workspace_bytes(ctypes.byref(geom), int(kx)))
-    ws = None
-    if need:
-        key = (gy.device.index, stream_ptr(gy.device))
-        ws = _wgrad_ws_cache.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty((need,), dtype=torch.uint8, device=gy.device)
-            _remember(_wgrad_ws_cache, key, ws)
+    ws = _stream_buffer(_wgrad_ws_cache, need, gy.device) if need else None
     out = torch.empty((geom.O, geom.C, geom.KH, geom.KW), dtype=torch.float32, device=gy.device)
     ho, wo = out_hw(geom)
     with _on(gy), _Timed('lsq_train_wgrad', 4 * gy.numel() + 8 * kx * act_plane_words(geom) + 4 * out.numel(),
@@ -709,7 +701,7 @@ def wgrad(planes: torch.Tensor, kx: int, xscales: torch.Tensor, gy: torch.Tensor
 
 
 # ---- the linear-layer library (include/lsq_hip_linear.h): a third shared object, loaded on first use
-_LINEAR_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib', 'liblsq_hip_linear.so')
+_LINEAR_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear.so')
 LINEAR_ABI_VERSION = 1
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -720,25 +712,20 @@ def linear_library_path() -> str:
     return _LINEAR_LIB_PATH
 
 
+def _declare_linear(handle):
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    handle.lsq_linear_abi_version.restype = i32
+    handle.lsq_linear_abi_version.argtypes = []
+    handle.lsq_linear_xnor.restype = i32
+    handle.lsq_linear_xnor.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, i64, i64, i64, vp, vp]
+
+
 def linear_lib():
     """Load (once) and return the linear-layer library; raises if it has not been built (no fallback, as ``lib()``)."""
     global _linear_lib
     if _linear_lib is None:
-        with _lock:
-            if _linear_lib is None:
-                if not os.path.exists(_LINEAR_LIB_PATH):
-                    raise LsqHipError(
-                        f'{_LINEAR_LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
-                        '(or `make -C ml-quant_amd/csrc/linear`). The HIP path has no fallback.')
-                handle = ctypes.CDLL(_LINEAR_LIB_PATH)
-                vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-                handle.lsq_linear_abi_version.restype = i32
-                handle.lsq_linear_abi_version.argtypes = []
-                handle.lsq_linear_xnor.restype = i32
-                handle.lsq_linear_xnor.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, i64, i64, i64, vp, vp]
-                if handle.lsq_linear_abi_version() != LINEAR_ABI_VERSION:
-                    raise LsqHipError('liblsq_hip_linear.so ABI version mismatch')
-                _linear_lib = handle
+        _linear_lib = _load(_LINEAR_LIB_PATH, 'csrc/linear', _declare_linear,
+                            'lsq_linear_abi_version', LINEAR_ABI_VERSION, 'liblsq_hip_linear.so')
     return _linear_lib
 
 
@@ -778,7 +765,7 @@ def linear_xnor(planes: torch.Tensor, kx: int, xscales: torch.Tensor, rows_per_s
 
 
 # ---- the fp-activation linear-layer library (include/lsq_hip_linear_fp.h): a fourth shared object, loaded on first use
-_LINEAR_FP_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib', 'liblsq_hip_linear_fp.so')
+_LINEAR_FP_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_fp.so')
 LINEAR_FP_ABI_VERSION = 1
 _linear_fp_lib = None
 
@@ -787,26 +774,21 @@ def linear_fp_library_path() -> str:
     return _LINEAR_FP_LIB_PATH
 
 
+def _declare_linear_fp(handle):
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    handle.lsq_linear_fp_abi_version.restype = i32
+    handle.lsq_linear_fp_abi_version.argtypes = []
+    handle.lsq_linear_signw.restype = i32
+    handle.lsq_linear_signw.argtypes = [vp, f32, vp, i32, vp, vp, i64, i64, i64, vp, vp]
+
+
 def linear_fp_lib():
     """Load (once) and return the fp-activation linear-layer library; raises if it has not been built (no fallback, as
     ``lib()``)."""
     global _linear_fp_lib
     if _linear_fp_lib is None:
-        with _lock:
-            if _linear_fp_lib is None:
-                if not os.path.exists(_LINEAR_FP_LIB_PATH):
-                    raise LsqHipError(
-                        f'{_LINEAR_FP_LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
-                        '(or `make -C ml-quant_amd/csrc/linear_fp`). The HIP path has no fallback.')
-                handle = ctypes.CDLL(_LINEAR_FP_LIB_PATH)
-                vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-                handle.lsq_linear_fp_abi_version.restype = i32
-                handle.lsq_linear_fp_abi_version.argtypes = []
-                handle.lsq_linear_signw.restype = i32
-                handle.lsq_linear_signw.argtypes = [vp, f32, vp, i32, vp, vp, i64, i64, i64, vp, vp]
-                if handle.lsq_linear_fp_abi_version() != LINEAR_FP_ABI_VERSION:
-                    raise LsqHipError('liblsq_hip_linear_fp.so ABI version mismatch')
-                _linear_fp_lib = handle
+        _linear_fp_lib = _load(_LINEAR_FP_LIB_PATH, 'csrc/linear_fp', _declare_linear_fp,
+                               'lsq_linear_fp_abi_version', LINEAR_FP_ABI_VERSION, 'liblsq_hip_linear_fp.so')
     return _linear_fp_lib
 
 
@@ -844,8 +826,7 @@ def linear_signw(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: to
 
 
 # ---- the linear-layer training library (include/lsq_hip_linear_train.h): a fifth shared object, loaded on first use
-_LINEAR_TRAIN_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib',
-                                      'liblsq_hip_linear_train.so')
+_LINEAR_TRAIN_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_train.so')
 LINEAR_TRAIN_ABI_VERSION = 1
 _linear_train_lib = None
 
@@ -854,29 +835,23 @@ def linear_train_library_path() -> str:
     return _LINEAR_TRAIN_LIB_PATH
 
 
+def _declare_linear_train(handle):
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    handle.lsq_linear_train_abi_version.restype = i32
+    handle.lsq_linear_train_abi_version.argtypes = []
+    handle.lsq_linear_signw_dgrad_workspace_bytes.restype = ctypes.c_size_t
+    handle.lsq_linear_signw_dgrad_workspace_bytes.argtypes = [i32, i64, i64]
+    handle.lsq_linear_signw_dgrad.restype = i32
+    handle.lsq_linear_signw_dgrad.argtypes = [vp, vp, i32, vp, i64, i64, i64, vp, vp, ctypes.c_size_t, vp]
+
+
 def linear_train_lib():
     """Load (once) and return the linear-layer training library; raises if it has not been built (no fallback, as
     ``lib()``)."""
     global _linear_train_lib
     if _linear_train_lib is None:
-        with _lock:
-            if _linear_train_lib is None:
-                path = linear_train_library_path()
-                if not os.path.exists(path):
-                    raise LsqHipError(
-                        f'{path} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
-                        '(or `make -C ml-quant_amd/csrc/linear_train`). The HIP path has no fallback.')
-                handle = ctypes.CDLL(path)
-                vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-                handle.lsq_linear_train_abi_version.restype = i32
-                handle.lsq_linear_train_abi_version.argtypes = []
-                handle.lsq_linear_signw_dgrad_workspace_bytes.restype = ctypes.c_size_t
-                handle.lsq_linear_signw_dgrad_workspace_bytes.argtypes = [i32, i64, i64]
-                handle.lsq_linear_signw_dgrad.restype = i32
-                handle.lsq_linear_signw_dgrad.argtypes = [vp, vp, i32, vp, i64, i64, i64, vp, vp, ctypes.c_size_t, vp]
-                if handle.lsq_linear_train_abi_version() != LINEAR_TRAIN_ABI_VERSION:
-                    raise LsqHipError('liblsq_hip_linear_train.so ABI version mismatch')
-                _linear_train_lib = handle
+        _linear_train_lib = _load(_LINEAR_TRAIN_LIB_PATH, 'csrc/linear_train', _declare_linear_train,
+                                  'lsq_linear_train_abi_version', LINEAR_TRAIN_ABI_VERSION, 'liblsq_hip_linear_train.so')
     return _linear_train_lib
 
 
@@ -907,13 +882,7 @@ def linear_signw_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Ten
         raise ValueError('lsq_linear_signw_dgrad: every operand on the same cuda device')
     tl = linear_train_lib()
     need = int(tl.lsq_linear_signw_dgrad_workspace_bytes(kw, F, O))
-    ws = None
-    if need:
-        key = (dev.index, stream_ptr(dev))
-        ws = _dgrad_ws_cache.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-            _remember(_dgrad_ws_cache, key, ws)
+    ws = _stream_buffer(_dgrad_ws_cache, need, dev) if need else None
     gx = torch.empty((M, F), dtype=torch.float32, device=dev)
     with _on(gx), _Timed('lsq_linear_signw_dgrad', 4 * M * O * kw + 8 * kw * nw * opad + 2 * need + 4 * M * F,
                          2 * 2 * M * F * O * kw):       # bf16 FLOPs: the hi and the lo pass of every plane
@@ -924,8 +893,7 @@ def linear_signw_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Ten
 
 
 # ---- the linear layer's weight-gradient library (include/lsq_hip_linear_wgrad.h): a sixth shared object, loaded on first use
-_LINEAR_WGRAD_LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib',
-                                      'liblsq_hip_linear_wgrad.so')
+_LINEAR_WGRAD_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_wgrad.so')
 LINEAR_WGRAD_ABI_VERSION = 1
 LINEAR_WGRAD_MAX_SAMPLES = 65535    # lsq_linear_signx_wgrad: N <= 65535 (the limit of lsq_quant_values)
 _linear_wgrad_lib = None
@@ -935,30 +903,24 @@ def linear_wgrad_library_path() -> str:
     return _LINEAR_WGRAD_LIB_PATH
 
 
+def _declare_linear_wgrad(handle):
+    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+    handle.lsq_linear_wgrad_abi_version.restype = i32
+    handle.lsq_linear_wgrad_abi_version.argtypes = []
+    handle.lsq_linear_signx_wgrad_workspace_bytes.restype = ctypes.c_size_t
+    handle.lsq_linear_signx_wgrad_workspace_bytes.argtypes = [i32, i64, i64, i64, i64]
+    handle.lsq_linear_signx_wgrad.restype = i32
+    handle.lsq_linear_signx_wgrad.argtypes = [vp, vp, i32, vp, ctypes.c_float, i64, i64, i64, i64, vp, vp,
+                                              ctypes.c_size_t, vp]
+
+
 def linear_wgrad_lib():
     """Load (once) and return the linear layer's weight-gradient library; raises if it has not been built (no fallback, as
     ``lib()``)."""
     global _linear_wgrad_lib
     if _linear_wgrad_lib is None:
-        with _lock:
-            if _linear_wgrad_lib is None:
-                path = linear_wgrad_library_path()
-                if not os.path.exists(path):
-                    raise LsqHipError(
-                        f'{path} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
-                        '(or `make -C ml-quant_amd/csrc/linear_wgrad`). The HIP path has no fallback.')
-                handle = ctypes.CDLL(path)
-                vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-                handle.lsq_linear_wgrad_abi_version.restype = i32
-                handle.lsq_linear_wgrad_abi_version.argtypes = []
-                handle.lsq_linear_signx_wgrad_workspace_bytes.restype = ctypes.c_size_t
-                handle.lsq_linear_signx_wgrad_workspace_bytes.argtypes = [i32, i64, i64, i64, i64]
-                handle.lsq_linear_signx_wgrad.restype = i32
-                handle.lsq_linear_signx_wgrad.argtypes = [vp, vp, i32, vp, ctypes.c_float, i64, i64, i64, i64, vp, vp,
-                                                          ctypes.c_size_t, vp]
-                if handle.lsq_linear_wgrad_abi_version() != LINEAR_WGRAD_ABI_VERSION:
-                    raise LsqHipError('liblsq_hip_linear_wgrad.so ABI version mismatch')
-                _linear_wgrad_lib = handle
+        _linear_wgrad_lib = _load(_LINEAR_WGRAD_LIB_PATH, 'csrc/linear_wgrad', _declare_linear_wgrad,
+                                  'lsq_linear_wgrad_abi_version', LINEAR_WGRAD_ABI_VERSION, 'liblsq_hip_linear_wgrad.so')
     return _linear_wgrad_lib
 
 
@@ -989,13 +951,7 @@ def linear_signx_wgrad(gy: torch.Tensor, x: torch.Tensor, xscales: torch.Tensor,
         raise ValueError('lsq_linear_signx_wgrad: every operand on the same cuda device')
     wl = linear_wgrad_lib()
     need = int(wl.lsq_linear_signx_wgrad_workspace_bytes(kx, N, T, F, O))
-    ws = None
-    if need:
-        key = (dev.index, stream_ptr(dev))
-        ws = _linear_wgrad_ws_cache.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-            _remember(_linear_wgrad_ws_cache, key, ws)
+    ws = _stream_buffer(_linear_wgrad_ws_cache, need, dev) if need else None
     gwq = torch.empty((O, F), dtype=torch.float32, device=dev)
     with _on(gwq), _Timed('lsq_linear_signx_wgrad', 4 * M * O + 4 * M * F + 4 * kx * N + 2 * need + 4 * O * F,
                           2 * 2 * M * F * O * kx):       # bf16 FLOPs: the hi and the lo pass of every plane

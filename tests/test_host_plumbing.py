@@ -191,3 +191,22 @@ def test_skip_training_task_on_the_gpu(tmp_path):
         kth, nxt = top[:, k - 1], top[:, k]
         fragile = ((tval - nxt).abs() < 2 * d) | ((tval - kth).abs() < 2 * d)     # samples whose membership in the top k can flip
         assert abs(results[1][name] - results[0][name]) <= float(fragile.float().mean()) + 1e-9, name
+
+
+def test_the_shared_mma_header_is_a_prerequisite_of_the_objects_that_include_it():
+    """csrc/linear/lsq_signw_mma.h is included by the three bf16 linear libraries: `make -n -W <header>` (a query: it
+    launches and builds nothing) after a build must want to recompile each one's object, and must not in csrc/train."""
+    csrc = os.path.join(ROOT, 'ml-quant_amd', 'csrc')
+    header = os.path.join(csrc, 'linear', 'lsq_signw_mma.h')
+    assert os.path.exists(header)
+
+    def compile_lines(sub):
+        subprocess.run(['make', '-C', os.path.join(csrc, sub)], check=True, capture_output=True)     # (nothing to do after build())
+        out = subprocess.run(['make', '-n', '-W', header, '-C', os.path.join(csrc, sub)], check=True, capture_output=True,
+                             text=True).stdout
+        return [line for line in out.splitlines() if ' -c ' in line]
+
+    for sub in ('linear_fp', 'linear_train', 'linear_wgrad'):
+        lines = compile_lines(sub)
+        assert len(lines) == 1 and f'lsq_{sub}.hip' in lines[0] and f'{sub}_lsq_{sub}.o' in lines[0], (sub, lines)
+    assert compile_lines('train') == []
