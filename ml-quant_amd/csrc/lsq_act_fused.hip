@@ -22,7 +22,8 @@
 // HBM traffic: two reads of the row (the second one of the short rows is served by L2 / Infinity Cache) instead
 // of three, one launch instead of three, no workspace.  Why 512 lanes: the per-lane working set of the solver is
 // the same whatever the number of lanes, so fewer lanes with 256 VGPRs each leave room for the resident keys
-// where 1024 lanes with 128 VGPRs spill; every kernel here has private_segment_fixed_size 0.
+// where 1024 lanes with 128 VGPRs spill.  The given-scale, gf-2 and non-windowed kernels have private_segment_fixed_size 0;
+// the windowed kernels spill a few hundred bytes per lane.
 // Anything the fixed-size tables cannot take (more than 40 flagged level-1 bins, table or list overflow) goes to a
 // block-level path that histograms straight from the row in memory: slow, general, exact.
 //
@@ -43,23 +44,6 @@
 #ifndef LSQ_WIN_HIST
 #define LSQ_WIN_HIST 0
 #endif
-// This file is compiled TWICE (Makefile): as it is -- fused_act_quant, rows in NCHW order -- and with -DLSQ_FUSED_S3=1 --
-// fused_act_quant_s3, the same kernels for rows in the THREE-STREAM layout (LSQ_LAYOUT_SPLIT3, include/lsq_hip.h: element
-// (c, pixel) in stream s = (c + pixel) % 3 at s * S + c * hp + pixel / 3, S = C * hp).  There the sub-sample e % 3 == 0 of
-// the v1 search (quantization.py:63, skip = 3; e = c * H W + pixel, H W % 3 == 1) is stream 0, the first contiguous third of
-// the row: pass 1 reads a third of the bytes (one float4 per four keys instead of three; the keys of a channel's block, the
-// pad at its end masked), pass 2 reads all three streams -- 4/3 reads of the row instead of 2.  The solve works on exact
-// integer sums and ranks keys by value, so WHICH lane holds a key does not matter; pass 2 sums every pixel's |r| in the
-// same channel order: planes and scales are the NCHW kernels' bit for bit.
-#ifndef LSQ_FUSED_S3
-#define LSQ_FUSED_S3 0
-#endif
-#if LSQ_FUSED_S3                                   // (developer builds: this translation unit's own phase-clock tables)
-#define g_fused_times g_fused_times_s3
-#define g_win_stats g_win_stats_s3
-#define lsq_debug_read_fused_times lsq_debug_read_fused_times_s3
-#define lsq_debug_read_win_stats lsq_debug_read_win_stats_s3
-#endif
 namespace lsq {
 #if defined(LSQ_PHASE_CLOCKS)
 __device__ long long g_fused_times[1024][16];    // constant-rate clock (100 MHz) at the phase marks of each workgroup
@@ -72,8 +56,6 @@ __device__ int g_win_stats[1024][4];             // windowed level 1: 1 solved /
 #define FMARK(i) do {} while (0)
 #endif
 namespace {
-
-constexpr bool kS3 = LSQ_FUSED_S3 != 0;        // rows in the three-stream layout (this translation unit's kernels)
 
 constexpr int kNzCap = 2048;                   // non-empty level-1 bins tested per chunk of the level-1 scan
 constexpr int kSlotCap = 64;                   // flagged level-1 bins per scan round (slot records)
@@ -360,34 +342,9 @@ static __device__ __forceinline__ unsigned l1_scan(FusedLds* lds, unsigned n, un
 
 // ---------------------------------------------------------------------------------------------
 // Block path: the sub-sampled keys of the row straight from memory (L2 / Infinity Cache).
-// three-stream rows: entries of channel c in stream 0 = pixels congruent to -c modulo 3 below H W
-static __device__ __forceinline__ unsigned s3_count(unsigned c, unsigned HW) {
-  const unsigned pmin = (3u - c % 3u) % 3u;
-  return (HW - pmin + 2u) / 3u;
-}
 template <class F>
 static __device__ __forceinline__ void for_each_row_key(const FusedArgs& a, const float* __restrict__ xrow, unsigned n, F f) {
   constexpr int U = 8;
-  if constexpr (kS3) {
-    // the sub-sample is stream 0: C blocks of x_hp floats, the first s3_count(c) of each are keys
-    const unsigned hp = (unsigned)a.x_hp, tot = (unsigned)a.C * hp, HW = (unsigned)(a.H * a.W);
-    for (unsigned j0 = threadIdx.x; j0 < tot; j0 += kThreads * U) {
-      float v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) v[u] = xrow[min(j0 + (unsigned)u * kThreads, tot - 1u)];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const unsigned j = j0 + (unsigned)u * kThreads;
-        const unsigned c = j / hp;
-        if (j < tot && j - c * hp < s3_count(c, HW)) {
-          float xv = v[u];
-          if (a.pre_scale) xv = fmaf(xv, a.pre_scale[c], a.pre_shift[c]);
-          f(abs_key(clamp_sym(xv, a.alpha)));
-        }
-      }
-    }
-    return;
-  }
   for (unsigned j0 = threadIdx.x; j0 < n; j0 += kThreads * U) {
     float v[U];
 #pragma unroll
@@ -1584,43 +1541,14 @@ struct Pf {
 // those loads until most of the 256 KB of its workgroup have arrived -- measured: the phase behind the request grew by
 // exactly what pass 2 saved.  An eighth at a time (32 KB per CU) fits, and the copy runs meanwhile.
 static constexpr int kPfParts = 8;
-// Three-stream rows: where a lane's item -- VEC pixels p0, p0 + 3, ... (one class mod 3: consecutive floats of a stream,
-// starting at a multiple of VEC: aligned loads) x 64 channels -- finds channel c0 + cc: stream (c0 + cc + p0) % 3 at
-// (c0 + cc) hp + p0 / 3, i.e. qb[cc % 3] + cc * hp from three per-lane pointers.
-struct S3Item {
-  const float* qb[3];
-  int step;                                                          // hp floats
-};
-static __device__ __forceinline__ S3Item s3_item(const FusedArgs& a, const float* __restrict__ xrow, int c0, int p0) {
-  const unsigned S = (unsigned)a.x_s3, hp = (unsigned)a.x_hp;
-  const unsigned u0 = (unsigned)(c0 + p0);
-  const unsigned r0 = u0 - 3u * (__umulhi(u0, 0xAAAAAAABu) >> 1);
-  const float* base = xrow + ((long long)c0 * hp + (__umulhi((unsigned)p0, 0xAAAAAAABu) >> 1));
-  S3Item it;
-  it.qb[0] = base + (long long)r0 * S;
-  it.qb[1] = base + (long long)(r0 == 2u ? 0u : r0 + 1u) * S;
-  it.qb[2] = base + (long long)(r0 == 0u ? 2u : r0 - 1u) * S;
-  it.step = (int)hp;
-  return it;
-}
-// item index -> (channel word j, first pixel p0) of a three-stream row: per word 3 * PG items, PG = ceil(HW / (3 VEC))
-// groups of 3 VEC consecutive pixels, item (g, s) = pixels 3 VEC g + s + 3 v
-template <int VEC>
-static __device__ __forceinline__ void s3_decode(int item, int PG, int& j, int& p0) {
-  j = item / (3 * PG);
-  const int idx = item - j * 3 * PG;
-  const int g = idx / 3;
-  p0 = 3 * VEC * g + (idx - 3 * g);
-}
-
 template <int VEC, int K>
-static __device__ __forceinline__ void pass2_request_part(const float* __restrict__ q0, int HW, Pf<VEC>& pf, const S3Item* s3 = nullptr) {
+static __device__ __forceinline__ void pass2_request_part(const float* __restrict__ q0, int HW, Pf<VEC>& pf) {
   constexpr int L = Pf<VEC>::PB * Pf<VEC>::UB;                       // loads of the whole request
   constexpr int lo = K * L / kPfParts, hi = (K + 1) * L / kPfParts;
 #pragma unroll
   for (int i = lo; i < hi; ++i) {
     constexpr int UB = Pf<VEC>::UB;
-    const float* __restrict__ q = kS3 ? s3->qb[i % 3] + (long long)i * s3->step : q0 + (long long)i * HW;
+    const float* __restrict__ q = q0 + (long long)i * HW;
     const int b = i / UB, u = i % UB;
     if constexpr (VEC == 4) {
       const float4 t = *reinterpret_cast<const float4*>(q);
@@ -1639,31 +1567,23 @@ template <int VEC>
 static __device__ __forceinline__ void pass2_request(const FusedArgs& a, const float* __restrict__ xrow, int item0, Pf<VEC>& pf,
                                                      unsigned parts) {
   const int HW = a.H * a.W;
-  const int PV = kS3 ? 3 * ((HW + 3 * VEC - 1) / (3 * VEC)) : (HW + VEC - 1) / VEC;
+  const int PV = (HW + VEC - 1) / VEC;
   const int items = a.Gt * PV;
   if (item0 >= items) return;
-  int j, p;
-  if constexpr (kS3) {
-    s3_decode<VEC>(item0, PV / 3, j, p);
-  } else {
-    j = item0 / PV;
-    p = (item0 - j * PV) * VEC;
-  }
+  const int j = item0 / PV;
+  const int p = (item0 - j * PV) * VEC;
   const int grp = j / a.Gg;
   const int jj = j - grp * a.Gg;
   const int c0 = grp * a.cg + jj * 64;
   const float* __restrict__ q = xrow + (long long)c0 * HW + p;
-  S3Item s3v;
-  if constexpr (kS3) s3v = s3_item(a, xrow, c0, p);
-  const S3Item* s3 = kS3 ? &s3v : nullptr;
-  if (parts & 1u) pass2_request_part<VEC, 0>(q, HW, pf, s3);           // (compile-time masks at every call site)
-  if (parts & 2u) pass2_request_part<VEC, 1>(q, HW, pf, s3);
-  if (parts & 4u) pass2_request_part<VEC, 2>(q, HW, pf, s3);
-  if (parts & 8u) pass2_request_part<VEC, 3>(q, HW, pf, s3);
-  if (parts & 16u) pass2_request_part<VEC, 4>(q, HW, pf, s3);
-  if (parts & 32u) pass2_request_part<VEC, 5>(q, HW, pf, s3);
-  if (parts & 64u) pass2_request_part<VEC, 6>(q, HW, pf, s3);
-  if (parts & 128u) pass2_request_part<VEC, 7>(q, HW, pf, s3);
+  if (parts & 1u) pass2_request_part<VEC, 0>(q, HW, pf);               // (compile-time masks at every call site)
+  if (parts & 2u) pass2_request_part<VEC, 1>(q, HW, pf);
+  if (parts & 4u) pass2_request_part<VEC, 2>(q, HW, pf);
+  if (parts & 8u) pass2_request_part<VEC, 3>(q, HW, pf);
+  if (parts & 16u) pass2_request_part<VEC, 4>(q, HW, pf);
+  if (parts & 32u) pass2_request_part<VEC, 5>(q, HW, pf);
+  if (parts & 64u) pass2_request_part<VEC, 6>(q, HW, pf);
+  if (parts & 128u) pass2_request_part<VEC, 7>(q, HW, pf);
 }
 
 // full 64-channel groups: every channel index is a compile-time constant.  PRE: the caller may hold the first batches
@@ -1674,9 +1594,8 @@ static __device__ __forceinline__ double pass2_full(const FusedArgs& a, const fl
                                                     unsigned long long* __restrict__ prow0, unsigned long long* __restrict__ prow1,
                                                     int item0, int item_step, const Pf<VEC>* pre = nullptr, bool have_pre = false) {
   const int HW = a.H * a.W;
-  const int PV = kS3 ? 3 * ((HW + 3 * VEC - 1) / (3 * VEC)) : (HW + VEC - 1) / VEC;
+  const int PV = (HW + VEC - 1) / VEC;
   const int items = a.Gt * PV;
-  constexpr int PSTEP = kS3 ? 3 : 1;                     // pixel stride of a lane's VEC values
   const float alpha = a.alpha >= 0.f ? a.alpha : INFINITY;
   double acc = 0.0;
   // loads per batch; two batches in flight.  One pixel per lane (the short rows): all 64 channels at once --
@@ -1686,19 +1605,12 @@ static __device__ __forceinline__ double pass2_full(const FusedArgs& a, const fl
   constexpr int PB = Pf<VEC>::PB;
   auto one_item = [&](int item, auto first_tag) {
     constexpr bool FIRST = decltype(first_tag)::value;    // the batches b < PB are already in `pre`
-    int j, p;
-    if constexpr (kS3) {
-      s3_decode<VEC>(item, PV / 3, j, p);
-    } else {
-      j = item / PV;
-      p = (item - j * PV) * VEC;
-    }
+    const int j = item / PV;
+    const int p = (item - j * PV) * VEC;
     const int grp = j / a.Gg;
     const int jj = j - grp * a.Gg;
     const int c0 = grp * a.cg + jj * 64;
     const float* __restrict__ src = xrow + (long long)c0 * HW + p;
-    S3Item s3v;
-    if constexpr (kS3) s3v = s3_item(a, xrow, c0, p);
     const float* __restrict__ bs = bn_s + c0;      // (LDS copies of the folded batch norm)
     const float* __restrict__ bt = bn_t + c0;
     unsigned w0[VEC][2], w1[VEC][2];
@@ -1710,13 +1622,9 @@ static __device__ __forceinline__ double pass2_full(const FusedArgs& a, const fl
     }
     float buf[2][UB][VEC];
     const float* __restrict__ q = src + (FIRST ? (long long)PB * UB * HW : 0ll);   // running channel pointer (no table of 64 addresses)
-    auto load = [&](int which, int bb) {
+    auto load = [&](int which, int) {
 #pragma unroll
       for (int u = 0; u < UB; ++u, q += HW) {
-        if constexpr (kS3) {
-          const int cc = bb * UB + u;
-          q = s3v.qb[cc % 3] + (long long)cc * s3v.step;
-        }
         if constexpr (VEC == 4) {
           const float4 t = *reinterpret_cast<const float4*>(q);
           buf[which][u][0] = t.x; buf[which][u][1 % VEC] = t.y; buf[which][u][2 % VEC] = t.z; buf[which][u][3 % VEC] = t.w;
@@ -1758,8 +1666,8 @@ static __device__ __forceinline__ double pass2_full(const FusedArgs& a, const fl
     }
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
-      const int pix = p + PSTEP * v;
-      if (!kS3 || pix < HW) acc += (double)facc[v];      // (three-stream rows: a value past the image belongs to the next channel)
+      acc += (double)facc[v];
+      const int pix = p + v;
       if (pix < HW) {
         const int h = pix / a.W;
         const int w = pix - h * a.W;
@@ -1865,7 +1773,7 @@ template <int U, int VEC, bool WIN>
 static __device__ __forceinline__ void run(const FusedArgs& a, FusedLds* lds) {
   const int row = blockIdx.x;
   const int tid = threadIdx.x;
-  const float* __restrict__ xrow = a.x + (long long)row * (kS3 ? 3ll * a.x_s3 : a.row_elems);
+  const float* __restrict__ xrow = a.x + (long long)row * a.row_elems;
   FMARK(0);
   for (int i = tid; i < L1_BINS; i += kThreads) lds->a.hist1[i] = 0ull;
   // windowed level-1 histogram (solve_windowed): fine bins over the binades below the clamp value, one bin per binade below them
@@ -1900,24 +1808,16 @@ static __device__ __forceinline__ void run(const FusedArgs& a, FusedLds* lds) {
     const float hinv = 1.0f / (float)HW;
     // triples in flight per lane (more in flight measured slower: the histogram atomics of a batch overlap the
     // loads of the next one)
-    constexpr int B = kS3 ? 9 : 3;                 // (three-stream rows: the same 144 bytes per lane in flight)
-    // three-stream rows: a lane's step is ONE float4 of stream 0 -- four entries of one channel's block, keys up to the
-    // channel's count (s3_count), a third of the bytes
-    const unsigned nvec0 = kS3 ? (unsigned)a.x_s3 / 4u : 0u, hp4 = kS3 ? (unsigned)a.x_hp / 4u : 1u;
-    const unsigned hp4_magic = (unsigned)((0x100000000ull + hp4 - 1u) / hp4);      // jt / hp4 = umulhi(jt, magic): exact while jt * hp4 < 2^32
+    constexpr int B = 3;
 #pragma unroll
     for (int u0 = 0; u0 < U; u0 += B) {
-      float4 v[B][kS3 ? 1 : 3];
+      float4 v[B][3];
 #pragma unroll
       for (int b = 0; b < B; ++b) {
         if (u0 + b < U) {
           const unsigned jt = (unsigned)tid + (unsigned)(u0 + b) * kThreads;
-          if constexpr (kS3) {
-            v[b][0] = row4[min(jt, nvec0 - 1u)];
-          } else {
 #pragma unroll
-            for (int t = 0; t < 3; ++t) v[b][t] = row4[min(3u * jt + (unsigned)t, nvec - 1u)];
-          }
+          for (int t = 0; t < 3; ++t) v[b][t] = row4[min(3u * jt + (unsigned)t, nvec - 1u)];
         }
       }
 #pragma unroll
@@ -1925,30 +1825,7 @@ static __device__ __forceinline__ void run(const FusedArgs& a, FusedLds* lds) {
         if (u0 + b < U) {
           const unsigned jt = (unsigned)tid + (unsigned)(u0 + b) * kThreads;
           const unsigned e0 = 12u * jt;
-          float xs[4] = {v[b][0].x, kS3 ? v[b][0].y : v[b][0].w, kS3 ? v[b][0].z : v[b][kS3 ? 0 : 1].z,
-                         kS3 ? v[b][0].w : v[b][kS3 ? 0 : 2].y};
-          if constexpr (kS3) {
-            const unsigned ch = min(__umulhi(jt, hp4_magic), (unsigned)a.C - 1u);
-            const unsigned t0 = 4u * (jt - ch * hp4), cnt = s3_count(ch, (unsigned)HW);
-            float sc = 1.f, sh = 0.f;
-            if (affine) {
-              sc = bn_lds ? lds->bn_s[ch] : a.pre_scale[ch];
-              sh = bn_lds ? lds->bn_t[ch] : a.pre_shift[ch];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const bool has = jt < nvec0 && t0 + (unsigned)e < cnt;
-              const unsigned key = abs_key(clamp_sym(affine ? fmaf(xs[e], sc, sh) : xs[e], a.alpha));
-              if (has) {
-                if (win) hist_add_win(lds, key, win_k0, win_sh, low_base);
-                else hist_add(lds, key);
-                mk = min(mk, key);
-                xk = max(xk, key);
-              }
-              kreg[4 * (u0 + b) + e] = has ? key : kNoKey;
-            }
-            continue;
-          }
+          float xs[4] = {v[b][0].x, v[b][0].w, v[b][1].z, v[b][2].y};
           if (affine) {
             // channel of element e0 (e0 / HW via a reciprocal, corrected); the other three sub-sampled elements
             // are at most one channel boundary further each (HW >= 4).  Scale / shift come from the LDS copy.
@@ -2211,7 +2088,6 @@ __global__ __launch_bounds__(T) void aq_greedy2_kernel(FusedArgs a) {
   }
 }
 
-#if !LSQ_FUSED_S3
 template <int T>
 int launch_greedy(const FusedArgs& a, int vec, hipStream_t st) {
   if (vec == 4) hipLaunchKernelGGL((aq_greedy2_kernel<T, 4>), dim3(a.N), dim3(T), 0, st, a);
@@ -2235,7 +2111,6 @@ int launch_forced(const FusedArgs& a, int vec, hipStream_t st) {
   else hipLaunchKernelGGL((aq_forced_kernel<T, 1>), grid, dim3(T), 0, st, a);
   return (int)hipGetLastError();
 }
-#endif
 
 template <int T, int U>
 int launch(const FusedArgs& a, int vec, hipStream_t st) {
@@ -2251,11 +2126,9 @@ int launch(const FusedArgs& a, int vec, hipStream_t st) {
     else if (vec == 2) hipLaunchKernelGGL((aq_fused_kernel<T, U, 2, true>), dim3(a.N), dim3(T), 0, st, a);
     else hipLaunchKernelGGL((aq_fused_kernel<T, U, 1, true>), dim3(a.N), dim3(T), 0, st, a);
   } else {
-#if !LSQ_FUSED_S3
     if (vec == 4) hipLaunchKernelGGL((aq_fused_kernel<T, U, 4, false>), dim3(a.N), dim3(T), 0, st, a);
     else if (vec == 2) hipLaunchKernelGGL((aq_fused_kernel<T, U, 2, false>), dim3(a.N), dim3(T), 0, st, a);
     else hipLaunchKernelGGL((aq_fused_kernel<T, U, 1, false>), dim3(a.N), dim3(T), 0, st, a);
-#endif
   }
 #endif
   return (int)hipGetLastError();
@@ -2263,19 +2136,8 @@ int launch(const FusedArgs& a, int vec, hipStream_t st) {
 
 }  // namespace
 
-#if LSQ_FUSED_S3
-int fused_act_quant_s3(const FusedArgs& a_in, hipStream_t st) {
-  FusedArgs a = a_in;
-  // three-stream rows: the solving kernels only (given scales and gf-2 read the row once as it is); H W = 3 h + 1, streams
-  // of S floats (a multiple of 4, at least ceil(M / 3) + 8: pass 2's last items read a few floats past a stream's end)
-  if (a.forced || a.greedy || a.x_s3 <= 0 || a.x_hp <= 0 || a.x_hp % 32 || a.x_s3 != (long long)a.C * a.x_hp ||
-      ((long long)a.H * a.W) % 3 != 1 || a.x_hp < ((long long)a.H * a.W + 2) / 3 + 3 || (a.cg & 63) != 0 || a.C > kBnCap)
-    return kFusedNotEligible;
-#else
 int fused_act_quant(const FusedArgs& a_in, hipStream_t st) {
   FusedArgs a = a_in;
-  if (a.x_s3) return kFusedNotEligible;
-#endif
   const long long HW = (long long)a.H * a.W;
   const long long M = a.row_elems;
   // windowed level-1 histogram of the solve (solve_windowed): under a symmetric clamp every key is at most key(alpha), so the
@@ -2298,42 +2160,31 @@ int fused_act_quant(const FusedArgs& a_in, hipStream_t st) {
   // address pass of the load path) or many rounds, two for the 1..4 rounds in between (56 x 56 x 64: 784 four-pixel
   // items on 512 lanes are two rounds with the second half empty)
   int vec = 1;
-  const long long items4 = kS3 ? (long long)a.Gt * 3 * ((HW + 11) / 12) : (long long)a.Gt * (HW / 4);
-  if ((kS3 || HW % 4 == 0) && (items4 <= T || items4 >= 4 * T)) vec = 4;
-  else if (kS3 || HW % 2 == 0) vec = 2;
-  if (kS3 && (long long)a.Gt * 3 * ((HW + 2) / 3) <= T) vec = 1;      // (the 7 x 7 rows: one pixel per lane, as the NCHW kernels)
+  const long long items4 = (long long)a.Gt * (HW / 4);
+  if (HW % 4 == 0 && (items4 <= T || items4 >= 4 * T)) vec = 4;
+  else if (HW % 2 == 0) vec = 2;
 #ifdef LSQ_TUNE
   if (const char* e = getenv("LSQ_FUSED_VEC")) {
     const int v = atoi(e);
     if ((v == 4 || v == 2 || v == 1) && HW % v == 0) vec = v;
   }
 #endif
-#if !LSQ_FUSED_S3
   if (a.forced) {
     if (a.N > 65535) return kFusedNotEligible;       // (grid y)
     // no rounds to balance here: the widest loads the image allows
     return launch_forced<T>(a, HW % 4 == 0 ? 4 : (HW % 2 == 0 ? 2 : 1), st);
   }
   if (a.greedy) return launch_greedy<T>(a, vec, st);
-#else
-  if (!a.win_sh) return kFusedNotEligible;           // (rows under a symmetric clamp: the windowed kernels, with their fall-back)
-#endif
-  const long long ntrip = kS3 ? a.x_s3 / 4 : (M / 4 + 2) / 3;
+  const long long ntrip = (M / 4 + 2) / 3;
   const long long need = (ntrip + T - 1) / T;        // triples (4 keys each) per lane
 #ifdef LSQ_DEV_U
   return need <= LSQ_DEV_U ? launch<T, LSQ_DEV_U>(a, vec, st) : kFusedNotEligible;
-#else
-#if LSQ_FUSED_S3
-  if (need <= 18) return launch<T, 18>(a, vec, st);     // (28 x 28 x 128: 128 blocks of 288 floats = 18 float4 per lane)
-  if (need <= 33) return launch<T, 33>(a, vec, st);
-  return kFusedNotEligible;
 #else
   if (need <= 5) return launch<T, 5>(a, vec, st);
   if (need <= 9) return launch<T, 9>(a, vec, st);
   if (need <= 17) return launch<T, 17>(a, vec, st);
   if (need <= 33) return launch<T, 33>(a, vec, st);
   return kFusedNotEligible;
-#endif
 #endif
 }
 

@@ -28,10 +28,6 @@ struct ConvArgs {
                                        // Infinity Cache and this is its last use (set by the entry point, kStreamBytes)
   int dbg_no_corr;                     // tuning builds only
   int int8_mfma;                       // test hook: the int8 matrix-core kernel instead of the fp4 one (two-plane, unchained launches)
-  // ---- three-stream rows (LSQ_LAYOUT_SPLIT3, include/lsq_hip.h): 0 = NCHW, else S = floats per stream of the tensor's rows
-  int y_s3;                            // layout of y (and of the partial sums read back with `accumulate`)
-  int res_s3;                          // layout of res_pre / res_post (both)
-  int s3_hp;                           // floats per channel of a stream (S = O * s3_hp)
   // ---- chained 1-bit layers (lsq_xnor_conv2d_chain): the NEXT layer's ls-1 quantizer in this layer's epilogue, and this
   // layer's activation scale from the exact row sum the PREVIOUS layer's epilogue left
   const long long* xunits;             // [N] or null: row sum of |clamp(x)| in units of 2^e; xscale = float(units * xunit / xM)
@@ -54,7 +50,6 @@ struct ConvArgs {
 constexpr long long kInfinityCacheBytes = 256ll << 20;
 
 constexpr int kXnorMfmaNotEligible = 1;
-constexpr int kXnorMfmaNoLayout = 2;     // a three-stream operand on a geometry without such a kernel: LSQ_E_UNSUPPORTED
 // One launch (one weight plane x kx <= 2 activation planes) on the matrix cores; kXnorMfmaNotEligible when the
 // geometry is not covered (the caller then takes the popcount kernel), else hipGetLastError().
 int xnor_conv_mfma(const ConvArgs& a, int kx, int groups, hipStream_t st);

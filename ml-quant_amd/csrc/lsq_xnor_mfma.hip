@@ -29,9 +29,6 @@
 #include <type_traits>
 
 #include "lsq_xnor_conv.h"
-#ifndef LSQ_Y3_WAVES
-#define LSQ_Y3_WAVES 12
-#endif
 
 namespace lsq {
 namespace {
@@ -50,33 +47,16 @@ constexpr unsigned kM0 = 0x01010101u;
 // 512 channels (the fragments of 512 channels fill the LDS of a CU; at 256 channels one workgroup of 8 waves expands
 // the weights and builds the tables ONCE where two workgroups of 4 did it twice: 59-60 -> 55-56 us per 14 x 14 layer, round 4).
 //
-// S3: kernels that read / write fp32 tensors in the THREE-STREAM ROW layout (include/lsq_hip.h, LSQ_LAYOUT_SPLIT3): element
-// (c, pixel) of a sample's row lives in stream s = (c + pixel) % 3 at s * S + c * hp + pixel / 3 (hp floats per channel and
-// stream, a multiple of 32; S = C * hp), so that the sub-sample e % 3 == 0 of the flat NCHW index e = c * HoWo + pixel --
-// what the next layer's scale solve reads (quantization.py:63, skip = 3) -- is ONE contiguous third of the row instead of
-// every third float of all of it: HoWo % 3 == 1 (every ResNet shape), hence e % 3 = (c + pixel) % 3.
-// When the OUTPUT has that layout a tile is 32 pixels at stride 3 of ONE image -- pixel 96 group + j + 3 lane, j = 0, 1, 2,
-// ceil(HoWo / 96) groups per image --, so the 32 lanes of a channel's store are 32 consecutive floats of one stream that
-// START ON A 128-BYTE LINE (the first version -- e at (e % 3) S + e / 3, groups running across images -- had them start
-// anywhere: every line was written by two tiles on two CUs, and the launch took 110 us against 75).  The bit-plane reads
-// of such a tile are the 32 lanes' 24-byte windows back to back: 768 bytes without overlap where 32 neighbouring pixels share
-// all but 272 -- so the three tiles of a group, which read the same lines shifted by one word, go to three waves of ONE
-// workgroup at the same time (wave = (slot, j), NWAVES = 6: two groups per workgroup and round) and meet in the CU's L1; on
-// three different CUs (the first version) the planes went through the L2s 2.8 times and the 56 x 56 layers took 141 us
-// against 92.  Residual operands may have either layout.
-//
 // FP4 (round 6): the same kernel on v_mfma_scale_f32_32x32x64_f8f6f4 with both operands in fp4 (E2M1) and unit block scales --
 // the matrix cores' fastest format, twice the int8 rate (MI355X_MICROARCH.md: 9.1 PF measured against 4.4 POP/s), and
 // still EXACT here: a sign bit of the packed word becomes an fp4 code with ONE v_and_b32 per EIGHT channels -- nibble j of
 // register q of a lane is channel q + 4 j of its dword, `d & (0x11111111 << q)` holds codes 1 / 2 / 4 = 0.5 / 1 / 2 (q = 3 would
 // be the sign bit: that register is `(d >> 3) & 0x11111111`, 0.5 again) --, the weight nibble of the same slot is +-(4, 2, 1,
-// 4), so every product is +-2 or 0 and the fp32 accumulator, started at the border term fc, IS (b * s): integers below 2^13,
+// 4), so every product is +-2 or 0 and the fp32 accumulator, started at the border term fc, IS (b * s): integers below 2^14,
 // exact in any order.  Half the operand-build instructions, half the MFMAs and half the LDS bytes per binary MAC;
 // scripts/ubench/fp4_mfma_check.hip is the known-answer test of the instruction (subnormal code 1 = 0.5 included).
-template <int KX, int GG, int TAPS, int NWAVES, int WPC, bool CHAIN, bool YS3, bool RS3, bool FP4>
+template <int KX, int GG, int TAPS, int NWAVES, int WPC, bool CHAIN, bool FP4>
 __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a) {
-  constexpr bool S3 = YS3 || RS3;                // (which operands have the three-stream layout is fixed per instantiation:
-                                                 //  runtime selects between two sets of sixteen channel offsets cost scalar registers)
   constexpr int NT = 64 * NWAVES;
   constexpr int FPS = FP4 ? 1 : 2;               // 16-byte weight fragments per (word, tap) step: int8 K = 32 twice, fp4 K = 64 once
   constexpr int NF = TAPS * GG * FPS;            // 16-byte operand fragments per lane
@@ -96,19 +76,12 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
   // ---- tile bookkeeping (before the tables: the first loads go out early) --------------------------------------
   const unsigned total = (unsigned)(a.N * a.Ho * a.Wo);
   const int HoWo = a.Ho * a.Wo;
-  constexpr bool map3 = YS3;                     // tiles of 32 pixels at stride 3: the output is a three-stream tensor
-  // (stride-3 tiles: `tile` counts GROUPS of 96 pixels, the wave's j picks its third)
-  const int GPI = (HoWo + 95) / 96;              // stride-3 tiles: groups per image
-  const int ntiles = map3 ? a.N * GPI : (int)((total + 31u) >> 5);
-  constexpr int kSlots = map3 ? NWAVES / 3 : NWAVES;       // tiles (groups) a workgroup works on at a time
-  static_assert(!map3 || NWAVES % 3 == 0, "stride-3 tiles: three waves per group");
-  const int wslot = map3 ? wid / 3 : wid, j3 = map3 ? wid - 3 * (wid / 3) : 0;
-  const unsigned s3_S = (unsigned)(a.y_s3 ? a.y_s3 : a.res_s3), s3_h = (unsigned)a.s3_hp;      // floats per stream / per channel of a stream
+  const int ntiles = (int)((total + 31u) >> 5);
   const unsigned* __restrict__ xd = reinterpret_cast<const unsigned*>(a.xplanes);
   const unsigned plane_stride = 2u * (unsigned)a.xplane_words;
-  const int tstride = gridDim.x * kSlots;
+  const int tstride = gridDim.x * NWAVES;
   // a wave's pixel index advances by the same amount from tile to tile: (n, ho, wo) follow with adds and carries
-  const unsigned dstep = (map3 ? 96u : 32u) * (unsigned)tstride;
+  const unsigned dstep = 32u * (unsigned)tstride;
   const int d_n = (int)(dstep / (unsigned)HoWo);
   const int d_r = (int)(dstep - (unsigned)d_n * (unsigned)HoWo);
   const int d_ho = d_r / a.Wo, d_wo = d_r - d_ho * a.Wo;
@@ -156,56 +129,15 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
       }
   };
 
-  // Element offset of (sample, out-channel o0 + ob + k, the lane's pixel) = v[k % 3] + koff(k), koff uniform: NCHW
-  // v[.] = ((n O + o0 + ob) HoWo + pixel), koff = k HoWo; three streams: with u = o0 + ob + pixel, channel k sits in stream
-  // (u + k) % 3 at (o0 + ob + k) hp + pixel / 3 -- so v[m] = n * 3 S + ((u + m) % 3) S + (o0 + ob) hp + pixel / 3, koff = k hp.
-  struct Lay {
-    unsigned v[S3 ? 3 : 1];
-  };
-  auto lay_of = [&](unsigned pix, int ln, bool s3, Lay& L) {
-    if constexpr (S3) {
-      if (s3) {
-        const unsigned u0 = (unsigned)(o0 + ob) + pix;
-        const unsigned r0 = u0 - 3u * (__umulhi(u0, 0xAAAAAAABu) >> 1);
-        const unsigned base = (unsigned)ln * 3u * s3_S + (unsigned)(o0 + ob) * s3_h + (__umulhi(pix, 0xAAAAAAABu) >> 1);
-        L.v[0] = base + r0 * s3_S;
-        L.v[1] = base + (r0 == 2u ? 0u : r0 + 1u) * s3_S;
-        L.v[2] = base + (r0 == 0u ? 2u : r0 - 1u) * s3_S;
-        return;
-      }
-    }
-    const unsigned yoff = (unsigned)((ln * a.O + o0 + ob) * HoWo) + pix;
-#pragma unroll
-    for (int m = 0; m < (S3 ? 3 : 1); ++m) L.v[m] = yoff;
-  };
-  constexpr bool y_s3 = YS3, r_s3 = RS3;
-  // (uniform) element offset of register i's channel k = (i & 3) + 8 (i >> 2) on top of Lay::v[k % 3]
-  auto koff = [&](int i, bool s3) -> long long {
-    const int k = (i & 3) + 8 * (i >> 2);
-    return (S3 && s3) ? (long long)k * s3_h : (long long)k * HoWo;
-  };
-  auto kv = [&](const Lay& L, int i) -> unsigned { return L.v[S3 ? ((i & 3) + 8 * (i >> 2)) % 3 : 0]; };
+  // (uniform) element offset of register i's out-channel (i & 3) + 8 (i >> 2) on top of the lane's own
+  auto koff = [&](int i) -> long long { return (long long)((i & 3) + 8 * (i >> 2)) * HoWo; };
 
   // wave-major numbering: when the tiles do not divide evenly, the waves with one tile more sit in different
   // workgroups (on different SIMDs) instead of filling one
-  int tile = wslot * gridDim.x + blockIdx.x;
+  int tile = wid * gridDim.x + blockIdx.x;
   const bool have_tile = tile < ntiles;
-  // stride-3 tiles: group `t` = (image t / GPI, group t % GPI of that image); lanes past the image's last pixel (its last
-  // group: 3136 = 32 * 96 + 64) are marked like the lanes past the last pixel of all, n = N
-  auto pix3 = [&](int t) {
-    const int gn = t / GPI, gi = t - gn * GPI;
-    const int p = 96 * gi + j3 + 3 * col;
-    Pix px;
-    const bool in = p < HoWo;
-    px.n = in ? gn : a.N;
-    px.ho = in ? (int)((unsigned)p / (unsigned)a.Wo) : 0;
-    px.wo = in ? p - px.ho * a.Wo : 0;
-    return px;
-  };
   Pix cur;
-  if constexpr (map3) {
-    cur = pix3(tile);
-  } else {
+  {
     const unsigned p = (unsigned)tile * 32u + (unsigned)col;
     cur.n = (int)(p / (unsigned)HoWo);
     const int r = (int)(p - (unsigned)cur.n * (unsigned)HoWo);
@@ -344,23 +276,14 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
     const int nxt = tile + tstride;
     const bool more = nxt < ntiles;
     Pix nx = cur;
-    if (more) {
-      if constexpr (map3) nx = pix3(nxt);
-      else advance(nx);
-    }
+    if (more) advance(nx);
 
     // What the epilogue reads from memory is requested NOW, a whole tile of MFMAs ahead: the two waves of a SIMD run
     // in lockstep (same start, same tile length), so a load waited for in the epilogue stalls the matrix core for
     // its full latency -- that, not the MFMA rate, set the pace of the first version.
     const int ln = cur.n < a.N ? cur.n : 0;
     // 32-bit element offsets from uniform bases (the entry point admits outputs below 2^30 elements)
-    // (three-stream kernels: the offsets are worked out where they are used -- here for the loads, again in front of the
-    //  stores from an opaque copy of the pixel -- instead of living through the MFMA loop: the 128-channel kernel sits at
-    //  its 168-register budget)
-    Lay ly, lr;
-    unsigned pixv = (unsigned)(cur.ho * a.Wo + cur.wo);
-    lay_of(pixv, ln, y_s3, ly);
-    lay_of(pixv, ln, r_s3, lr);
+    const unsigned yoff = (unsigned)((ln * a.O + o0 + ob) * HoWo) + (unsigned)(cur.ho * a.Wo + cur.wo);
     float xs[KX], rv[16], basev[16];
     // (int8: the accumulators hold 32 (b * s), hence xs / 32 -- exact; fp4: they hold (b * s) itself)
     constexpr float kAccUnit = FP4 ? 1.0f : 0.03125f;
@@ -372,10 +295,10 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
       const float* __restrict__ rsrc = want_pre ? a.res_pre : a.res_post;
       if (a.res_stream) {           // (uniform) last use of a tensor that does not fit the Infinity Cache next to the output: lsq_xnor_conv.h
 #pragma unroll
-        for (int i = 0; i < 16; ++i) rv[i] = __builtin_nontemporal_load(rsrc + koff(i, r_s3) + kv(lr, i));
+        for (int i = 0; i < 16; ++i) rv[i] = __builtin_nontemporal_load(rsrc + koff(i) + yoff);
       } else {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) rv[i] = (rsrc + koff(i, r_s3))[kv(lr, i)];
+        for (int i = 0; i < 16; ++i) rv[i] = (rsrc + koff(i))[yoff];
       }
     } else {
 #pragma unroll
@@ -383,7 +306,7 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
     }
     if (acc_in) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i) basev[i] = (a.y + koff(i, y_s3))[kv(ly, i)];
+      for (int i = 0; i < 16; ++i) basev[i] = (a.y + koff(i))[yoff];
     } else {
 #pragma unroll
       for (int i = 0; i < 16; ++i) basev[i] = s_bias[ob + (i & 3) + 8 * (i >> 2)];
@@ -496,11 +419,6 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
 #pragma unroll
       for (int i = 0; i < 16; ++i) nqv[i] = 0.f;
     }
-    if constexpr (S3) {
-      asm volatile("" : "+v"(pixv));
-      lay_of(pixv, ln, y_s3, ly);
-      if (want_post && want_pre) lay_of(pixv, ln, r_s3, lr);
-    }
     if (cur.n < a.N) {                           // (false only for the lanes past the last pixel)
       // float(acc) = 32 * (b * s) exactly (|.| < 2^18) and xs / 32 is exact, so (xs / 32) * float(acc) is the very
       // product xs * float(b * s) of the popcount kernel
@@ -545,14 +463,14 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
       }
       if (want_post && want_pre) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) outv[i] += (a.res_post + koff(i, r_s3))[kv(lr, i)];
+        for (int i = 0; i < 16; ++i) outv[i] += (a.res_post + koff(i))[yoff];
       }
 #ifdef LSQ_XNOR_CLOCKS
       asm volatile("" :: "v"(outv[0]), "v"(outv[15]));
       XCLK();
 #endif
 #pragma unroll
-      for (int i = 0; i < 16; ++i) (a.y + koff(i, y_s3))[kv(ly, i)] = outv[i];
+      for (int i = 0; i < 16; ++i) (a.y + koff(i))[yoff] = outv[i];
       if constexpr (CHAIN) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) nqv[i] = outv[i];
@@ -624,23 +542,6 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
 #endif
 }
 
-// three-stream OUTPUT: workgroups of six waves (two groups of 96 pixels at a time), two per CU -- the same three waves per
-// SIMD and 168 registers as the NCHW kernels
-template <int KX, int GG>
-int launch_y3(const ConvArgs& a, hipStream_t st) {
-  constexpr int NWAVES = LSQ_Y3_WAVES, WPC = 3, kSlots = NWAVES / 3;   // (WPC: waves per SIMD the registers must allow)
-  const long long total = (long long)a.N * a.Ho * a.Wo;
-  const long long ngroups = (long long)a.N * (((long long)a.Ho * a.Wo + 95) / 96);
-  const int n_ot = a.O / 32;
-  long long gx = (256 * (12 / NWAVES) + n_ot - 1) / n_ot;
-  if (gx * kSlots > ngroups) gx = (ngroups + kSlots - 1) / kSlots;
-  gx = gx < 1 ? 1 : gx;
-  const dim3 grid((unsigned)gx, (unsigned)n_ot), block(64 * NWAVES);
-  if (a.res_s3) hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, true, true, true>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, true, false, true>), grid, block, 0, st, a);
-  return (int)hipGetLastError();
-}
-
 template <int KX, int GG, bool FP4 = true>
 int launch(const ConvArgs& a, hipStream_t st) {
   // launch shape per channel count: waves per workgroup, workgroups per CU, and WPC = the waves per SIMD the register
@@ -671,25 +572,13 @@ int launch(const ConvArgs& a, hipStream_t st) {
   long long gx = (wgs + n_ot - 1) / n_ot;
   gx = gx < 1 ? 1 : gx;
   if (gx * NWAVES > ntiles) gx = (ntiles + NWAVES - 1) / NWAVES;
-  if constexpr (FP4) if (a.y_s3 || a.res_s3) {
-    // three-stream tensors: the two-plane kernels of 64 / 128 channels (the 56 x 56 and 28 x 28 layers of the network, whose
-    // rows are the long ones); a three-stream OUTPUT means tiles at pixel stride 3, whose bookkeeping wants the tile stride
-    // of a wave to be a multiple of 3
-    if constexpr (KX == 2 && GG <= 2) {
-      if (a.y_s3) return launch_y3<KX, GG>(a, st);
-      hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, false, true, true>), dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), 0, st, a);
-      return (int)hipGetLastError();
-    } else {
-      return kXnorMfmaNoLayout;
-    }
-  }
   if constexpr (!FP4) {
-    hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, false, false, false>), dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), 0, st, a);
+    hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, false>), dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), 0, st, a);
   } else {
     if (KX == 1 && (a.xunits || a.nq_planes32))
-      hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, KX == 1, false, false, true>), dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), 0, st, a);
+      hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, KX == 1, true>), dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), 0, st, a);
     else
-      hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, false, false, true>), dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), 0, st, a);
+      hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, true>), dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), 0, st, a);
   }
   return (int)hipGetLastError();
 }
@@ -697,7 +586,7 @@ int launch(const ConvArgs& a, hipStream_t st) {
 template <int KX>
 int launch_gg(const ConvArgs& a, hipStream_t st) {
   // (test hook lsq_debug_xnor_impl(2): rounds 2-5's int8 kernel, the fp4 kernel's comparator -- same bits; plain calls only)
-  if (a.int8_mfma && !a.y_s3 && !a.res_s3 && !a.xunits && !a.nq_planes32) {
+  if (a.int8_mfma && !a.xunits && !a.nq_planes32) {
     switch (a.cg) {
       case 64: return launch<KX, 1, false>(a, st);
       case 128: return launch<KX, 2, false>(a, st);
