@@ -667,6 +667,47 @@ def wgrad(planes: torch.Tensor, kx: int, xscales: torch.Tensor, gy: torch.Tensor
     return out
 
 
+def _check_linear(what: str, dims: dict, fp32: dict, int64: Optional[dict] = None, int32: Optional[dict] = None,
+                  bad: bool = False, wplanes: Optional[tuple] = None, mismatch=None,
+                  bias: Optional[torch.Tensor] = None) -> None:
+    """The host-side operand checks of the linear entry points (``what`` names one), in one order; the first that fails
+    raises.  TypeError: an operand of ``fp32`` / ``int64`` / ``int32`` = {name: tensor}, or ``bias``, of another dtype.  Then
+    ValueError ``'<what>: ...'``:
+      * operands that are not ``contiguous``;
+      * ``bad sizes``: an entry of ``dims`` = {name: size} that is not positive, or ``bad`` (the caller's element counts
+        against the dims);
+      * operands that ``do not match``: ``wplanes`` = (wbits, wscales, F, O), the sign planes / scales [kw, O] lsq_pack_weight
+        took and wrote for (O, F, 1, 1); then ``mismatch()``, the caller's own (what does not match, or None);
+      * a ``bias`` of other than ``dims['O']`` elements;
+      * last -- so that every check above can be reached with CPU tensors -- operands not all on the same ``cuda device``."""
+    if bias is not None:
+        fp32 = dict(fp32, bias=bias)
+    groups = ((torch.float32, fp32), (torch.int64, int64 or {}), (torch.int32, int32 or {}))
+    for dtype, named in groups:
+        wrong = [name for name, t in named.items() if t.dtype != dtype]
+        if wrong:
+            raise TypeError(f'{what}: {", ".join(wrong)} must be {dtype} tensors')
+    tensors = [t for _, named in groups for t in named.values()]
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: operands must be contiguous')
+    if bad or min(dims.values()) <= 0:
+        raise ValueError(f'{what}: bad sizes ' + ' '.join(f'{name}={v}' for name, v in dims.items()) + ' for '
+                         + ', '.join(f'{name} of {t.numel()}' for name, t in fp32.items()) + ' elements')
+    if wplanes is not None:
+        wbits, wscales, F, O = wplanes
+        if wscales.dim() != 2 or wscales.shape[1] != O \
+                or wbits.numel() != wscales.shape[0] * ((F + 63) // 64) * ((O + 15) // 16 * 16):
+            raise ValueError(f'{what}: weight planes / scales do not match (kw, F, O)')
+    problem = None if mismatch is None else mismatch()
+    if problem is not None:
+        raise ValueError(f'{what}: {problem} do not match')
+    if bias is not None and bias.numel() != dims['O']:
+        raise ValueError(f'{what}: bias must have O elements')
+    dev = tensors[0].device
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError(f'{what}: every operand on the same cuda device')
+
+
 # ---- the linear-layer library (include/lsq_hip_linear.h): a third shared object, loaded on first use
 _LINEAR_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear.so')
 LINEAR_ABI_VERSION = 1
@@ -701,28 +742,17 @@ def linear_xnor(planes: torch.Tensor, kx: int, xscales: torch.Tensor, rows_per_s
     """y [M, O] = F.linear(x_q, w_q, bias) from sign planes (lsq_linear_xnor): ``planes`` / ``xscales`` [kx, M / rows_per_scale]
     are what lsq_act_quant wrote for (N, rows_per_scale * F, 1, 1), ``wbits`` / ``wsum`` / ``wscales`` [kw, O] what
     lsq_pack_weight took and wrote for (O, F, 1, 1).  Bit for bit the 1x1 lsq_xnor_conv2d over (M, F, 1, 1)."""
-    if planes.dtype != torch.int64 or wbits.dtype != torch.int64 or wsum.dtype != torch.int32:
-        raise TypeError('planes and wbits are int64 tensors, wsum an int32 tensor')
-    xscales, wscales = _f32c(xscales), _f32c(wscales)
-    if bias is not None:
-        bias = _f32c(bias)
-    tensors = [planes, xscales, wbits, wsum, wscales] + ([] if bias is None else [bias])
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError('lsq_linear_xnor: operands must be contiguous')
-    dev = planes.device
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError('lsq_linear_xnor: every operand on the same cuda device')
     M, F, O, kx, t = int(M), int(F), int(O), int(kx), int(rows_per_scale)
-    if min(M, F, O, kx, t) <= 0 or M % t:
-        raise ValueError(f'lsq_linear_xnor: bad sizes M={M} F={F} O={O} kx={kx} rows_per_scale={t}')
-    nw, kw = (F + 63) // 64, wscales.shape[0]
-    opad = (O + 15) // 16 * 16
-    if planes.numel() < kx * M * nw or xscales.numel() != kx * (M // t):
-        raise ValueError('lsq_linear_xnor: activation planes / scales do not match (kx, M, F)')
-    if wscales.dim() != 2 or wscales.shape[1] != O or wbits.numel() != kw * nw * opad or wsum.numel() != kw * O:
-        raise ValueError('lsq_linear_xnor: weight planes / sums / scales do not match (O, F)')
-    if bias is not None and bias.numel() != O:
-        raise ValueError('lsq_linear_xnor: bias must have O elements')
+    # (scales and a bias of another layout are copied, as the convolution's are)
+    xscales, wscales, bias = _f32c(xscales), _f32c(wscales), None if bias is None else _f32c(bias)
+    nw, dev = (F + 63) // 64, planes.device
+    _check_linear('lsq_linear_xnor', {'M': M, 'F': F, 'O': O, 'kx': kx, 'rows_per_scale': t},
+                  {'xscales': xscales, 'wscales': wscales}, {'planes': planes, 'wbits': wbits}, {'wsum': wsum},
+                  bad=t > 0 and M % t != 0, wplanes=(wbits, wscales, F, O), bias=bias,
+                  mismatch=lambda: ('activation planes / scales and (kx, M, F)'
+                                    if planes.numel() < kx * M * nw or xscales.numel() != kx * (M // t) else
+                                    'weight sums and (kw, O)' if wsum.numel() != wscales.shape[0] * O else None))
+    kw = wscales.shape[0]
     y = torch.empty((M, O), dtype=torch.float32, device=dev)
     with _on(y), _Timed('lsq_linear_xnor', M * kx * nw * 8 + 4 * M * O, M * O * F * kx * kw):
         check(linear_lib().lsq_linear_xnor(planes.data_ptr(), kx, xscales.data_ptr(), t, wbits.data_ptr(), wsum.data_ptr(),
@@ -764,25 +794,10 @@ def linear_signw(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: to
     """y [M, O] = F.linear(clamp(x), w_q, bias) for fp32 rows ``x`` [M, F] (any 4-byte-aligned data pointer) and the sign
     planes ``wbits`` / scales ``wscales`` [kw, O] lsq_pack_weight took and wrote for (O, F, 1, 1) (lsq_linear_signw);
     ``alpha`` is the symmetric clamp bound, negative for none."""
-    if x.dtype != torch.float32 or wscales.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
-        raise TypeError('x, wscales and bias are fp32 tensors')
-    if wbits.dtype != torch.int64:
-        raise TypeError('wbits is an int64 tensor')
-    tensors = [x, wbits, wscales] + ([] if bias is None else [bias])
-    dev = x.device
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError('lsq_linear_signw: every operand on the same cuda device')
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError('lsq_linear_signw: operands must be contiguous')
     M, F, O = int(M), int(F), int(O)
-    if min(M, F, O) <= 0 or x.numel() != M * F:
-        raise ValueError(f'lsq_linear_signw: bad sizes M={M} F={F} O={O} for x of {x.numel()} elements')
-    nw, opad = (F + 63) // 64, (O + 15) // 16 * 16
-    kw = wscales.shape[0] if wscales.dim() == 2 else 0
-    if wscales.dim() != 2 or wscales.shape[1] != O or wbits.numel() != kw * nw * opad:
-        raise ValueError('lsq_linear_signw: weight planes / scales do not match (O, F)')
-    if bias is not None and bias.numel() != O:
-        raise ValueError('lsq_linear_signw: bias must have O elements')
+    _check_linear('lsq_linear_signw', {'M': M, 'F': F, 'O': O}, {'x': x, 'wscales': wscales}, {'wbits': wbits},
+                  bad=x.numel() != M * F, wplanes=(wbits, wscales, F, O), bias=bias)
+    kw, nw, opad, dev = wscales.shape[0], (F + 63) // 64, (O + 15) // 16 * 16, x.device
     y = torch.empty((M, O), dtype=torch.float32, device=dev)
     launches = (kw + 1) // 2                         # (y is read back by every launch after the first)
     with _on(y), _Timed('lsq_linear_signw', 4 * M * F * launches + 8 * kw * nw * opad + 4 * M * O * (2 * launches - 1),
@@ -830,23 +845,10 @@ def linear_signw_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Ten
     ``wbits`` / scales ``wscales`` [kw, O] lsq_pack_weight took and wrote for (O, F, 1, 1) -- the forward's own operands
     (lsq_linear_signw_dgrad).  The transposed plane image lives in a workspace cached per (device, stream) like the
     solver's (rewritten by every call; kernels of one stream run in order)."""
-    if gy.dtype != torch.float32 or wscales.dtype != torch.float32:
-        raise TypeError('gy and wscales are fp32 tensors')
-    if wbits.dtype != torch.int64:
-        raise TypeError('wbits is an int64 tensor')
-    tensors = [gy, wbits, wscales]
-    dev = gy.device
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError('lsq_linear_signw_dgrad: operands must be contiguous')
     M, F, O = int(M), int(F), int(O)
-    if min(M, F, O) <= 0 or gy.numel() != M * O:
-        raise ValueError(f'lsq_linear_signw_dgrad: bad sizes M={M} F={F} O={O} for gy of {gy.numel()} elements')
-    nw, opad = (F + 63) // 64, (O + 15) // 16 * 16
-    kw = wscales.shape[0] if wscales.dim() == 2 else 0
-    if wscales.dim() != 2 or wscales.shape[1] != O or wbits.numel() != kw * nw * opad:
-        raise ValueError('lsq_linear_signw_dgrad: weight planes / scales do not match (O, F)')
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError('lsq_linear_signw_dgrad: every operand on the same cuda device')
+    _check_linear('lsq_linear_signw_dgrad', {'M': M, 'F': F, 'O': O}, {'gy': gy, 'wscales': wscales}, {'wbits': wbits},
+                  bad=gy.numel() != M * O, wplanes=(wbits, wscales, F, O))
+    kw, nw, opad, dev = wscales.shape[0], (F + 63) // 64, (O + 15) // 16 * 16, gy.device
     tl = linear_train_lib()
     need = int(tl.lsq_linear_signw_dgrad_workspace_bytes(kw, F, O))
     ws = _stream_buffer(_dgrad_ws_cache, need, dev) if need else None
@@ -900,22 +902,12 @@ def linear_signx_wgrad(gy: torch.Tensor, x: torch.Tensor, xscales: torch.Tensor,
     ``x`` [N * T, F] before the clamp and the per-(plane, sample) scales ``xscales`` [kx, N] of its quantizer
     (lsq_linear_signx_wgrad): x_q is never written, its signs go into a bit image in a workspace cached per (device, stream)
     like the solver's (rewritten by every call; kernels of one stream run in order)."""
-    if gy.dtype != torch.float32 or x.dtype != torch.float32 or xscales.dtype != torch.float32:
-        raise TypeError('gy, x and xscales are fp32 tensors')
-    tensors = [gy, x, xscales]
-    dev = gy.device
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError('lsq_linear_signx_wgrad: operands must be contiguous')
     N, T, F, O = int(N), int(T), int(F), int(O)
     M = N * T
-    if min(N, T, F, O) <= 0 or gy.numel() != M * O or x.numel() != M * F:
-        raise ValueError(f'lsq_linear_signx_wgrad: bad sizes N={N} T={T} F={F} O={O} for gy of {gy.numel()} and x of '
-                         f'{x.numel()} elements')
-    kx = xscales.shape[0] if xscales.dim() == 2 else 0
-    if xscales.dim() != 2 or xscales.shape[1] != N:
-        raise ValueError('lsq_linear_signx_wgrad: activation scales do not match (kx, N)')
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError('lsq_linear_signx_wgrad: every operand on the same cuda device')
+    _check_linear('lsq_linear_signx_wgrad', {'N': N, 'T': T, 'F': F, 'O': O}, {'gy': gy, 'x': x, 'xscales': xscales},
+                  bad=gy.numel() != M * O or x.numel() != M * F,
+                  mismatch=lambda: 'activation scales and (kx, N)' if xscales.dim() != 2 or xscales.shape[1] != N else None)
+    kx, dev = xscales.shape[0], gy.device
     wl = linear_wgrad_lib()
     need = int(wl.lsq_linear_signx_wgrad_workspace_bytes(kx, N, T, F, O))
     ws = _stream_buffer(_linear_wgrad_ws_cache, need, dev) if need else None

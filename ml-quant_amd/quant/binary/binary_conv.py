@@ -16,87 +16,30 @@ Dispatch of ``forward``:
     ``quant.binary.hip_train`` for the backward (straight-through estimator, transposed sign-weight convolution), one
     ``torch.autograd.Function`` per call;
   * anything else (CPU tensors, grouped / dilated training convolutions) -> the torch formulation in ``quant.binary``.
+
+Construction, the quantizer / clamp factories, cache invalidation, workspace retention and the eval-side activation
+quantization are ``quant.binary.hip_module.HipQuantModule``'s, shared with ``QuantLinear``; this file keeps what is the
+convolution's own: the kernels' limits, packed weights, the folded batch norm, chaining and the fused epilogue.
 """
 
-import re
-from collections import defaultdict
-from functools import partial
-from typing import Any, Callable, Dict, List, Optional, Tuple, Union
+from typing import Any, Dict, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-import quant.binary.activation_quantization as activation_quantization
-import quant.binary.quantization as quantization
-import quant.binary.weight_quantization as weight_quantization
-
-_SCHEME_RE = re.compile(r'fp|ls-1|ls-2|ls-T|gf-\d+')
+from quant.binary.hip_module import HipQuantModule
 
 
-class QuantConv2d(nn.Conv2d):
+class QuantConv2d(HipQuantModule, nn.Conv2d):
     """``Conv2d(x_quant(clamp(x)), w_quant(w))`` with schemes fp | ls-1 | ls-2 | ls-T | gf-k."""
-
-    #: sub-sampling stride of the activation v1 search (quantizer_ls_2 / ls_ternary default)
-    act_skip = 3
 
     def __init__(self, x_quant: str, w_quant: str, in_channels: int, out_channels: int,
                  kernel_size: Union[int, Tuple[int, int]], clamp: Optional[Dict] = None,
                  moving_average_mode: str = 'off', moving_average_momentum: float = 0.99,
                  **kwargs: Any) -> None:
-        super().__init__(in_channels, out_channels, kernel_size, **kwargs)
-        self.x_quant, self.w_quant = x_quant, w_quant
-        self.x_approximate = self._get_x_quantizer(x_quant, moving_average_mode, moving_average_momentum)
-        self.w_approximate = self._get_w_quantizer(w_quant, out_channels)
-        self.clamp_config = dict(clamp) if clamp is not None else {'kind': 'identity'}
-        self.clamping_fn = self._get_clamper(**self.clamp_config)
-
-        self.quantized_parameters: Dict[str, List[torch.Tensor]] = defaultdict(list)
-        if self.bias is not None:
-            self.quantized_parameters['fp'].append(self.bias)
-        self.quantized_parameters[w_quant].append(self.weight)
-
-        self._hip_cache: Dict[str, Any] = {}          # packed weights, workspaces (never in state_dict)
-
-    # ------------------------------------------------------------------ factories
-    @staticmethod
-    def _validate_scheme(scheme: str) -> None:
-        if not isinstance(scheme, str) or not _SCHEME_RE.fullmatch(scheme):
-            raise ValueError(f'Scheme {scheme} is invalid. Please see docs for valid schemes.')
-
-    @staticmethod
-    def _get_x_quantizer(scheme: str, moving_average_mode: str = 'off',
-                         moving_average_momentum: float = 0.99) -> nn.Module:
-        QuantConv2d._validate_scheme(scheme)
-        if scheme == 'fp':
-            return quantization.QuantizerFP()
-        if scheme.startswith('gf-'):
-            return activation_quantization.ActivationQuantizerGF(
-                int(scheme[3:]), moving_average_mode, moving_average_momentum)
-        cls = {'ls-1': activation_quantization.ActivationQuantizerLS1,
-               'ls-2': activation_quantization.ActivationQuantizerLS2,
-               'ls-T': activation_quantization.ActivationQuantizerLST}[scheme]
-        return cls(moving_average_mode, moving_average_momentum)
-
-    @staticmethod
-    def _get_w_quantizer(scheme: str, size: int) -> nn.Module:
-        QuantConv2d._validate_scheme(scheme)
-        if scheme == 'fp':
-            return quantization.QuantizerFP()
-        if scheme.startswith('gf-'):
-            return weight_quantization.WeightQuantizerGF(size, int(scheme[3:]))
-        cls = {'ls-1': weight_quantization.WeightQuantizerLS1,
-               'ls-2': weight_quantization.WeightQuantizerLS2,
-               'ls-T': weight_quantization.WeightQuantizerLST}[scheme]
-        return cls(size)
-
-    @staticmethod
-    def _get_clamper(kind: str, alpha: float = 2) -> Callable[[torch.Tensor], torch.Tensor]:
-        if kind == 'identity':
-            return quantization.clamp_identity
-        if kind == 'symmetric':
-            return partial(quantization.clamp_symmetric, alpha=alpha)
-        raise ValueError(f'{kind} is not a valid clamping function.')
+        super().__init__(x_quant, w_quant, clamp, moving_average_mode, moving_average_momentum,
+                         in_channels, out_channels, kernel_size, **kwargs)
 
     # ------------------------------------------------------------------ forward
     #: train-mode CUDA tensors through the kernels (False: the torch formulation, e.g. to compare the two in tests)
@@ -156,30 +99,7 @@ class QuantConv2d(nn.Conv2d):
                     return False
         return True
 
-    def _replicate_for_data_parallel(self):
-        replica = super()._replicate_for_data_parallel()
-        replica._hip_cache = {}           # packed weights / workspaces live on the replica's own device
-        return replica
-
-    def train(self, mode: bool = True):
-        if mode:
-            self._hip_cache.clear()       # weights (and cached scales) may change
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self._hip_cache.clear()
-        return super()._load_from_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._hip_cache.clear()
-        return super()._apply(fn, *args, **kwargs)
-
     # ------------------------------------------------------------------ HIP path
-    def _alpha(self) -> float:
-        if self.clamp_config.get('kind') == 'symmetric':
-            return float(self.clamp_config.get('alpha', 2))
-        return -1.0
-
     def _packed_weights(self, geom, _hip):
         wq = self.w_approximate
         bufs = wq.cached_scales()
@@ -261,43 +181,14 @@ class QuantConv2d(nn.Conv2d):
             return None
         pre = None if bn is None else conv._folded_bn(bn)
         ph, pw = conv.padding
-        key = ('pre', n, self.out_channels, ho, wo, ph, pw, device, _hip.stream_ptr(device))
-        planes = conv._hip_cache.get(key)
-        if planes is None:
-            words = n * (self.out_channels // 64) * (ho + 2 * ph) * (wo + 2 * pw)
-            planes = torch.zeros((words,), dtype=torch.int64, device=device)          # zero halo; the interior is rewritten
-            stale = [kk for kk in list(conv._hip_cache) if isinstance(kk, tuple) and kk[0] == 'pre']
-            for kk in stale[:max(0, len(stale) - 3)]:
-                conv._hip_cache.pop(kk, None)
-            conv._hip_cache[key] = planes
+        words = n * (self.out_channels // 64) * (ho + 2 * ph) * (wo + 2 * pw)
+        planes = conv._workspace('pre', (n, self.out_channels, ho, wo, ph, pw, device, _hip.stream_ptr(device)),
+                                 lambda: torch.zeros((words,), dtype=torch.int64, device=device))   # zero halo; the interior is rewritten
         units = chain.accumulator(n, device)
         nxt = _hip.NextLs1(planes.data_ptr(), units.data_ptr(), None if pre is None else pre[0].data_ptr(),
                            None if pre is None else pre[1].data_ptr(), conv._alpha(), ph, pw)
         keep = (planes, units, pre)
         return nxt, chain.PreQuant(conv, bn, planes, units, (n, self.out_channels, ho, wo), _hip.stream_ptr(device)), keep
-
-    def _act_planes(self, x, geom, k, n, pre, xq, _hip):
-        """Quantize ``x`` with lsq_act_quant into this module's plane workspace; returns (planes, scales)."""
-        # (one workspace per launch stream: two streams through one module must not share planes and scales)
-        key = ('act', geom.key()[:4], geom.pad_h, geom.pad_w, self.groups, k, x.device,
-               _hip.stream_ptr(x.device))
-        ws = self._hip_cache.get(key)
-        if ws is None:
-            words = _hip.act_plane_words(geom)
-            # halo words must be zero; the kernels only ever write the interior
-            ws = (torch.zeros((k * words,), dtype=torch.int64, device=x.device),
-                  torch.empty((k, n), dtype=torch.float32, device=x.device))
-            # one plane workspace per input shape; serving with many batch sizes must not grow without bound
-            stale = [kk for kk in list(self._hip_cache) if isinstance(kk, tuple) and kk[0] == 'act']
-            for kk in stale[:max(0, len(stale) - 3)]:
-                self._hip_cache.pop(kk, None)
-            self._hip_cache[key] = ws
-        planes, scales = ws
-        forced = xq.eval_scales(n)
-        if forced is not None:
-            forced = forced.to(device=x.device, dtype=torch.float32).contiguous()
-        _hip.act_quant(x, geom, xq.hip_scheme, k, self.act_skip, self._alpha(), planes, scales, forced, pre)
-        return planes, scales
 
     def _forward_hip(self, x: torch.Tensor, pre_bn: Optional[nn.BatchNorm2d] = None, relu: bool = False,
                      res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
@@ -340,7 +231,7 @@ class QuantConv2d(nn.Conv2d):
                 if handed is not None:
                     planes_in, units_in = handed.planes, handed.units
                 else:
-                    planes_in, scales_in = self._act_planes(x, geom, k, n, pre, xq, _hip)
+                    planes_in, scales_in = self._act_planes(x, geom, k, _hip, (geom.pad_h, geom.pad_w, self.groups), pre)
                 join()
                 if _hip.xnor_conv2d_chain(planes_in, scales_in, units_in, self._alpha(), wbits, wsum, wscales, bias, geom, y,
                                           relu, res_pre, res_post, prelu, None if target is None else target[0]):
@@ -352,7 +243,7 @@ class QuantConv2d(nn.Conv2d):
                     _hip.xnor_conv2d(planes_in, k, scales_in, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu)
                     self.last_act_scales = scales_in
                     return y
-        planes, scales = self._act_planes(x, geom, k, n, pre, xq, _hip)
+        planes, scales = self._act_planes(x, geom, k, _hip, (geom.pad_h, geom.pad_w, self.groups), pre)
         join()
         _hip.xnor_conv2d(planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu)
         self.last_act_scales = scales

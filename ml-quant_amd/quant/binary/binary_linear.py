@@ -3,7 +3,8 @@
 The linear counterpart of ``QuantConv2d``: the same schemes (fp | ls-1 | ls-2 | ls-T | gf-k), constructor arguments
 (``x_quant, w_quant, in_features, out_features, clamp, moving_average_mode, moving_average_momentum`` then ``bias``),
 attributes (``x_approximate``, ``w_approximate``, ``clamping_fn``, ``quantized_parameters``), quantizer buffer names and
-``ValueError``s; the factories are ``QuantConv2d``'s own.
+``ValueError``s; construction, the factories, cache invalidation, workspace retention and the eval-side activation
+quantization are ``quant.binary.hip_module.HipQuantModule``'s, shared with ``QuantConv2d``.
 
 Semantics are those of the quantizer modules: an activation row is one SAMPLE, ``x.view(N, -1)`` in x's own element
 order, quantized on the 4-D view ``(N, T*F, 1, 1)`` (T = the product of the dimensions between the batch and the
@@ -26,39 +27,22 @@ Dispatch of ``forward``:
     the same 4-D views.
 """
 
-from collections import defaultdict
-from typing import Any, Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from quant.binary.binary_conv import QuantConv2d
+from quant.binary.hip_module import HipQuantModule
 
 
-class QuantLinear(nn.Linear):
+class QuantLinear(HipQuantModule, nn.Linear):
     """``Linear(x_quant(clamp(x)), w_quant(w))`` with schemes fp | ls-1 | ls-2 | ls-T | gf-k."""
-
-    #: sub-sampling stride of the activation v1 search (as QuantConv2d)
-    act_skip = QuantConv2d.act_skip
 
     def __init__(self, x_quant: str, w_quant: str, in_features: int, out_features: int, clamp: Optional[Dict] = None,
                  moving_average_mode: str = 'off', moving_average_momentum: float = 0.99, bias: bool = True) -> None:
-        super().__init__(in_features, out_features, bias=bias)
-        self.x_quant, self.w_quant = x_quant, w_quant
-        self.x_approximate = QuantConv2d._get_x_quantizer(x_quant, moving_average_mode, moving_average_momentum)
-        self.w_approximate = QuantConv2d._get_w_quantizer(w_quant, out_features)
-        self.clamp_config = dict(clamp) if clamp is not None else {'kind': 'identity'}
-        self.clamping_fn = QuantConv2d._get_clamper(**self.clamp_config)
-
-        self.quantized_parameters: Dict[str, List[torch.Tensor]] = defaultdict(list)
-        if self.bias is not None:
-            self.quantized_parameters['fp'].append(self.bias)
-        self.quantized_parameters[w_quant].append(self.weight)
-
-        self._hip_cache: Dict[str, Any] = {}          # packed weights, plane workspaces (never in state_dict)
-
-    _alpha = QuantConv2d._alpha                       # symmetric clamp bound, or -1 for the identity
+        super().__init__(x_quant, w_quant, clamp, moving_average_mode, moving_average_momentum,
+                         in_features, out_features, bias=bias)
 
     # ------------------------------------------------------------------ forward
     #: train-mode CUDA tensors through the kernels (quant.binary.hip_train_linear).  False: the torch formulation, the
@@ -124,24 +108,6 @@ class QuantLinear(nn.Linear):
             return False
         return True
 
-    def _replicate_for_data_parallel(self):
-        replica = super()._replicate_for_data_parallel()
-        replica._hip_cache = {}
-        return replica
-
-    def train(self, mode: bool = True):
-        if mode:
-            self._hip_cache.clear()       # weights (and cached scales) may change
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self._hip_cache.clear()
-        return super()._load_from_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._hip_cache.clear()
-        return super()._apply(fn, *args, **kwargs)
-
     # ------------------------------------------------------------------ HIP path
     def _packed_weights(self, _hip):
         """Weight sign planes of (O, F, 1, 1), packed once per eval session (re-packed when the weight or a scale changes)."""
@@ -158,26 +124,6 @@ class QuantLinear(nn.Linear):
             hit = (stamp, wbits, wsum.view(scales.shape[0], o), scales)
             self._hip_cache['w'] = hit
         return hit[1], hit[2], hit[3]
-
-    def _act_planes(self, x2, geom, k, _hip):
-        """lsq_act_quant of the rows ``x2`` [N, T*F] into this module's plane workspace; returns (planes, scales)."""
-        n = geom.N
-        key = ('act', geom.key()[:4], k, x2.device, _hip.stream_ptr(x2.device))
-        ws = self._hip_cache.get(key)
-        if ws is None:
-            ws = (torch.zeros((k * _hip.act_plane_words(geom),), dtype=torch.int64, device=x2.device),
-                  torch.empty((k, n), dtype=torch.float32, device=x2.device))
-            stale = [kk for kk in list(self._hip_cache) if isinstance(kk, tuple) and kk[0] == 'act']
-            for kk in stale[:max(0, len(stale) - 3)]:
-                self._hip_cache.pop(kk, None)
-            self._hip_cache[key] = ws
-        planes, scales = ws
-        xq = self.x_approximate
-        forced = xq.eval_scales(n)
-        if forced is not None:
-            forced = forced.to(device=x2.device, dtype=torch.float32).contiguous()
-        _hip.act_quant(x2, geom, xq.hip_scheme, k, self.act_skip, self._alpha(), planes, scales, forced)
-        return planes, scales
 
     def _forward_hip(self, x: torch.Tensor) -> torch.Tensor:
         from quant import _hip

@@ -25,13 +25,17 @@ backward  grad_bias = sum of grad_y;
           grad_w    = ``lsq_ste_backward`` over the weight rows.
 Geometries the transposed convolution does not take (groups, dilation, strides other than 1 / 2) fall back to the torch
 formulation of the module; results are those of the reference's graph within fp32 reassociation (tests: f9_train).
+The forward's weight side and activation side (forced scales, moving averages) and the module's plane workspace are
+``quant.binary.hip_train_common``'s, shared with ``hip_train_linear``; its retention policy is ``HipQuantModule._workspace``.
 """
 
 from typing import List, Optional
 
 import torch
-import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
+
+from quant.binary.hip_module import zero_planes
+from quant.binary.hip_train_common import step_act_quant, step_planes, step_weight_planes
 
 # binary activations: the weight gradient on lsq_train_wgrad (True) or on lsq_quant_values + conv2d_weight (False).  Off by
 # default: the batch-256 ResNet-18 train step measured slower with the kernel than with MIOpen (DESIGN 4.7,
@@ -93,52 +97,27 @@ class _QuantConv2dStep(torch.autograd.Function):
         alpha = conv._alpha()
         geom = _hip.make_geom(n, c, h, w, conv.out_channels, kh, kw, conv.stride, conv.padding, conv.dilation, 1)
         ho, wo = _hip.out_hw(geom)
-        # weight scales: computed from the detached weights and cached in the module's buffers (train mode)
-        with torch.no_grad():
-            conv.w_approximate(weight.detach())
-            wscales = conv.w_approximate.plane_scales().to(torch.float32).contiguous()          # [planes, O]
-        wbits, wsum = _hip.pack_weight(weight.detach(), geom, wscales)
+        wscales, wbits, wsum = step_weight_planes(conv, weight.detach(), geom, _hip)
         y = torch.empty((n, conv.out_channels, ho, wo), dtype=torch.float32, device=x.device)
         b = None if bias is None else bias.detach()
-        xq_mod = conv.x_approximate
         if conv.x_quant == 'fp':
             _hip.signw_conv2d(x.detach(), alpha, wbits, wscales, b, geom, y)
             xscales = None
         else:
-            k = xq_mod.n_planes
-            # the plane workspace is the module's, one per input shape and launch stream as in eval mode (zero halo written
-            # once, the kernels rewrite the interior); the scales are saved for backward and stay a tensor of this step
-            key = ('train_planes', geom.key()[:4], geom.pad_h, geom.pad_w, k, x.device, _hip.stream_ptr(x.device))
-            planes = conv._hip_cache.get(key)
+            k = conv.x_approximate.n_planes
             if WGRAD_KERNEL and ctx.needs_input_grad[1]:
                 # backward reads these planes: a buffer of this step (zero halo), saved with it
-                planes = torch.zeros((k * _hip.act_plane_words(geom),), dtype=torch.int64, device=x.device)
-            elif planes is None:
-                planes = torch.zeros((k * _hip.act_plane_words(geom),), dtype=torch.int64, device=x.device)
-                stale = [kk for kk in list(conv._hip_cache) if isinstance(kk, tuple) and kk[0] == 'train_planes']
-                for kk in stale[:max(0, len(stale) - 3)]:
-                    conv._hip_cache.pop(kk, None)
-                conv._hip_cache[key] = planes
-            xscales = torch.empty((k, n), dtype=torch.float32, device=x.device)
-            forced = xq_mod._forced_scales
-            forced = None if forced is None else xq_mod.plane_scales(forced).to(device=x.device, dtype=torch.float32).contiguous()
-            _hip.act_quant(x.detach(), geom, xq_mod.hip_scheme, k, conv.act_skip, alpha, planes, xscales, forced)
-            # moving averages (activation_quantization.py:72-88): tracked from the batch's mean scales; 'train_and_eval'
-            # quantizes with the tracked values
-            from quant.binary.activation_quantization import MovingAverageMode
-            if forced is None and xq_mod.moving_average_mode != MovingAverageMode.off:
-                with torch.no_grad():
-                    tracked = xq_mod.moving_avg_module(xscales[:xq_mod.num_scaling_factors].mean(1))
-                if xq_mod.moving_average_mode == MovingAverageMode.train_and_eval:
-                    forced = xq_mod.plane_scales(tracked.view(-1, 1).expand(-1, n)).to(torch.float32).contiguous()
-                    _hip.act_quant(x.detach(), geom, xq_mod.hip_scheme, k, conv.act_skip, alpha, planes, xscales, forced)
+                planes = zero_planes(geom, k, x.device, _hip)
+            else:
+                planes = step_planes(conv, geom, k, x.device, _hip, (geom.pad_h, geom.pad_w))
+            xscales = step_act_quant(conv, x.detach(), geom, planes, _hip)
             _hip.xnor_conv2d(planes, k, xscales, wbits, wsum, wscales, b, geom, y)
             conv.last_act_scales = xscales
         ctx.conv, ctx.geom, ctx.alpha = conv, geom, alpha
         ctx.has_bias = bias is not None
-        step_planes = planes if (xscales is not None and WGRAD_KERNEL and ctx.needs_input_grad[1]) else None
+        saved_planes = planes if (xscales is not None and WGRAD_KERNEL and ctx.needs_input_grad[1]) else None
         ctx.save_for_backward(x, weight, wscales, xscales if xscales is not None else x.new_empty(0),
-                              step_planes if step_planes is not None else x.new_empty(0, dtype=torch.int64))
+                              saved_planes if saved_planes is not None else x.new_empty(0, dtype=torch.int64))
         return y
 
     @staticmethod

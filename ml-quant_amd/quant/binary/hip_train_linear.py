@@ -23,12 +23,16 @@ backward  grad_bias = sum over the rows of grad_y;
           grad_w    = ``lsq_ste_backward`` over the weight rows.
 Nothing is computed for an input that needs no gradient.  Results are those of the torch formulation within fp32
 reassociation and the bf16 hi + lo split of the kernels (tests: test_gpu_linear_train.py).
+The forward's weight side and activation side (forced scales, moving averages) and the module's plane workspace are
+``quant.binary.hip_train_common``'s, shared with ``hip_train``; its retention policy is ``HipQuantModule._workspace``.
 """
 
 import os
 
 import torch
 from torch.autograd.function import once_differentiable
+
+from quant.binary.hip_train_common import step_act_quant, step_planes, step_weight_planes
 
 # True: the weight gradient of a layer with binary activations runs on lsq_linear_signx_wgrad (sign image + bf16 hi + lo
 # GEMM on the matrix cores) instead of lsq_quant_values + torch.mm -- the counterpart of hip_train.WGRAD_KERNEL; DESIGN 4.13
@@ -54,20 +58,6 @@ def supported(lin, x: torch.Tensor) -> bool:
     return lin._hip_supports(x)
 
 
-def _step_planes(lin, geom, k, device, _hip):
-    """The module's activation-plane workspace for train steps, one per row length and launch stream (the planes are
-    consumed by the forward GEMM alone: backward reads the saved scales, not the planes)."""
-    key = ('train_planes', geom.key()[:4], k, device, _hip.stream_ptr(device))
-    planes = lin._hip_cache.get(key)
-    if planes is None:
-        planes = torch.zeros((k * _hip.act_plane_words(geom),), dtype=torch.int64, device=device)
-        stale = [kk for kk in list(lin._hip_cache) if isinstance(kk, tuple) and kk[0] == 'train_planes']
-        for kk in stale[:max(0, len(stale) - 3)]:
-            lin._hip_cache.pop(kk, None)
-        lin._hip_cache[key] = planes
-    return planes
-
-
 class _QuantLinearStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, lin):
@@ -77,34 +67,17 @@ class _QuantLinearStep(torch.autograd.Function):
         f, o = lin.in_features, lin.out_features
         m = n * t
         alpha = lin._alpha()
-        # weight scales: computed from the detached weights and cached in the module's buffers (train mode)
-        with torch.no_grad():
-            lin.w_approximate(weight.detach().view(o, f, 1, 1))
-            wscales = lin.w_approximate.plane_scales().to(torch.float32).contiguous()           # [planes, O]
         wgeom = _hip.make_geom(1, f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
-        wbits, wsum = _hip.pack_weight(weight.detach().view(o, f, 1, 1), wgeom, wscales)
+        wscales, wbits, wsum = step_weight_planes(lin, weight.detach().view(o, f, 1, 1), wgeom, _hip)
         b = None if bias is None else bias.detach()
-        xq_mod = lin.x_approximate
         if lin.x_quant == 'fp':
             y = _hip.linear_signw(x.detach().view(m, f), alpha, wbits, wscales, b, m, f, o)
             xscales = None
         else:
-            k = xq_mod.n_planes
+            k = lin.x_approximate.n_planes
             geom = _hip.make_geom(n, t * f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
-            planes = _step_planes(lin, geom, k, x.device, _hip)
-            x2 = x.detach().view(n, t * f)
-            xscales = torch.empty((k, n), dtype=torch.float32, device=x.device)    # saved for backward: a tensor of this step
-            forced = xq_mod._forced_scales
-            forced = None if forced is None else xq_mod.plane_scales(forced).to(device=x.device, dtype=torch.float32).contiguous()
-            _hip.act_quant(x2, geom, xq_mod.hip_scheme, k, lin.act_skip, alpha, planes, xscales, forced)
-            # moving averages: tracked from the batch's mean scales; 'train_and_eval' quantizes with the tracked values
-            from quant.binary.activation_quantization import MovingAverageMode
-            if forced is None and xq_mod.moving_average_mode != MovingAverageMode.off:
-                with torch.no_grad():
-                    tracked = xq_mod.moving_avg_module(xscales[:xq_mod.num_scaling_factors].mean(1))
-                if xq_mod.moving_average_mode == MovingAverageMode.train_and_eval:
-                    forced = xq_mod.plane_scales(tracked.view(-1, 1).expand(-1, n)).to(torch.float32).contiguous()
-                    _hip.act_quant(x2, geom, xq_mod.hip_scheme, k, lin.act_skip, alpha, planes, xscales, forced)
+            planes = step_planes(lin, geom, k, x.device, _hip)
+            xscales = step_act_quant(lin, x.detach().view(n, t * f), geom, planes, _hip)
             y = _hip.linear_xnor(planes, k, xscales, t, wbits, wsum.view(wscales.shape[0], o), wscales, b, m, f, o)
             lin.last_act_scales = xscales
         ctx.alpha, ctx.dims = alpha, (n, t, f, o)

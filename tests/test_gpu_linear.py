@@ -226,3 +226,64 @@ def test_lenet_with_a_binary_fc1_end_to_end():
     with torch.no_grad():
         ref = F.log_softmax(model.fc2(F.relu(y_ref)), dim=1)
     assert ((logp - ref).abs().max() / ref.abs().max()).item() <= TOL
+
+
+# ------------------------------------------------------------------------------------------------ shared workspaces
+def _act_entries(m):
+    return [kk for kk in m._hip_cache if isinstance(kk, tuple) and kk[0] == 'act']
+
+
+@pytest.mark.parametrize('kind', ('conv', 'linear'))
+def test_workspace_eviction_keeps_every_batch_size_right(kind):
+    """Batch sizes 1..6 and 1 again through one eval-mode module: at most four plane workspaces are kept, and every output
+    has the bits of a fresh copy of the module (a workspace of another shape handed back, or an evicted one still in use,
+    would change them)."""
+    from quant.binary import QuantLinear
+    from quant.binary.binary_conv import QuantConv2d
+
+    def make():
+        if kind == 'conv':
+            return QuantConv2d('ls-2', 'ls-1', 64, 64, 3, CLAMP, padding=1), (64, 8, 8)
+        return QuantLinear('ls-2', 'ls-1', 128, 32, CLAMP), (128,)
+
+    m, row = make()
+    detgen.fill_module(m, seed=41)
+    with torch.no_grad():
+        m.w_approximate.v1.copy_(m.weight.abs().flatten(1).mean(1))       # (any positive scales do: the copies load the same state)
+    state = m.state_dict()
+    m.eval().to(DEV)
+    for step, n in enumerate((1, 2, 3, 4, 5, 6, 1)):
+        x = detgen.normal(f'evict.{kind}.{step}', (n, *row), scale=1.2).to(DEV)
+        fresh = make()[0]
+        fresh.load_state_dict(state)
+        fresh.eval().to(DEV)
+        with torch.no_grad():
+            y, ref = m(x), fresh(x)
+        assert 'w' in m._hip_cache and len(_act_entries(fresh)) == 1                 # both ran on the kernels
+        assert torch.equal(y.view(torch.int32), ref.view(torch.int32)), (kind, step, n)
+        assert len(_act_entries(m)) == min(step + 1, 4), (kind, step)
+
+
+def test_two_streams_through_one_quant_linear():
+    """One QuantLinear on two streams with different inputs, nothing between the launches: each stream has its own plane
+    workspace, and the results have the bits of the same calls on one stream."""
+    m = _module('ls-2', 'ls-1', 128, 32, seed=43).eval().to(DEV)
+    xa = detgen.normal('qlin.streams.a', (5, 128), scale=1.2).to(DEV)
+    xb = detgen.normal('qlin.streams.b', (5, 128), scale=0.7).to(DEV)
+    with torch.no_grad():
+        ya, yb = m(xa), m(xb)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    for kk in _act_entries(m):                 # (the packed weights stay: they were written on the stream that has just been waited for)
+        del m._hip_cache[kk]
+    with torch.no_grad():
+        with torch.cuda.stream(s1):
+            y1 = m(xa)
+        with torch.cuda.stream(s2):
+            y2 = m(xb)
+    torch.cuda.synchronize()
+    assert torch.equal(y1.view(torch.int32), ya.view(torch.int32)) and torch.equal(y2.view(torch.int32), yb.view(torch.int32))
+    keys = _act_entries(m)
+    assert len(keys) == 2 and {kk[-1] for kk in keys} == {s1.cuda_stream, s2.cuda_stream}
+    (p1, v1), (p2, v2) = (m._hip_cache[kk] for kk in keys)
+    assert p1.data_ptr() != p2.data_ptr() and v1.data_ptr() != v2.data_ptr()
