@@ -10,6 +10,8 @@
 //     accumulator.  The tiled kernels stage hi and lo rows of 64 k in LDS, kPitch bytes apart (mma_stage reads them).
 //   * B: the 8 sign bits of a lane's fragment are 8 consecutive bits (16 s + 8 h .. + 7 for k-step s) of one 64-bit word of
 //     its column and become 8 bf16 +-1.0 in registers (expand8).
+//   * 16-BIT A (csrc/linear_half, lsq_linear_signw_half): rows that already are bf16 or fp16 have no lo term: mma_stage1 reads
+//     one staged row set and issues one MFMA per k-step (mfma16; expand8_f16 for +-1.0 in fp16).
 //   * TILES: tile_rule picks one 32 x 32 tile per workgroup with the summed dimension split over kSplitWaves waves
 //     (split_reduce / split_sum add the partial sums in wave order), or 128 x 128 / 64 x 64 tiles of four waves.
 
@@ -134,6 +136,58 @@ __device__ __forceinline__ void mma_stage(const unsigned char* s_a, int lo_offse
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb)
           acc[q][rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[rb].v, bw[q][cb].v, acc[q][rb][cb], 0, 0, 0);
+  }
+}
+
+// ---- the single-term stage: an A operand that already IS 16-bit (bf16 or fp16 rows, csrc/linear_half) has no lo term
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+
+// expand8 for an fp16 A operand: element j = +-1.0 in fp16
+__device__ __forceinline__ Frag expand8_f16(unsigned bits) {
+  Frag f = expand8(bits);
+#pragma unroll
+  for (int d = 0; d < 4; ++d) f.u[d] = (f.u[d] & 0x80008000u) | 0x3C003C00u;
+  return f;
+}
+
+template <bool F16>
+__device__ __forceinline__ Frag expand8_as(unsigned bits) {
+  if constexpr (F16) return expand8_f16(bits);
+  else return expand8(bits);
+}
+
+// one k-step of 16 on fragments of 16-bit values: v_mfma_f32_32x32x16_f16 (F16) or v_mfma_f32_32x32x16_bf16
+template <bool F16>
+__device__ __forceinline__ f32x16 mfma16(const Frag& a, const Frag& b, f32x16 acc) {
+  if constexpr (F16)
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a.u), __builtin_bit_cast(f16x8, b.u), acc, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.v, b.v, acc, 0, 0, 0);
+}
+
+// mma_stage for a single-term A operand: the staged rows hold the 16-bit values themselves (one row set of kPitch bytes a
+// row, no lo rows), one MFMA per k-step and accumulator, in the order of mma_stage's hi products.
+template <bool F16, int NQ, int RB, int CB>
+__device__ __forceinline__ void mma_stage1(const unsigned char* s_a, int row0, int col, int hh,
+                                           const unsigned long long (&w)[NQ][CB], f32x16 (&acc)[NQ][RB][CB]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    Frag a[RB], bw[NQ][CB];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+      const uint4 v = *reinterpret_cast<const uint4*>(s_a + (row0 + rb * 32 + col) * kPitch + 32 * s + 16 * hh);
+      a[rb].u[0] = v.x; a[rb].u[1] = v.y; a[rb].u[2] = v.z; a[rb].u[3] = v.w;
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) bw[q][cb] = expand8_as<F16>((unsigned)(w[q][cb] >> (16 * s + 8 * hh)));
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+      for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) acc[q][rb][cb] = mfma16<F16>(a[rb], bw[q][cb], acc[q][rb][cb]);
   }
 }
 

@@ -920,6 +920,76 @@ def linear_signx_wgrad(gy: torch.Tensor, x: torch.Tensor, xscales: torch.Tensor,
     return gwq
 
 
+# ---- the 16-bit-activation linear-layer library (include/lsq_hip_linear_half.h): a seventh shared object, loaded on first use
+_LINEAR_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_half.so')
+LINEAR_HALF_ABI_VERSION = 1
+LINEAR_HALF_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}     # LSQ_DTYPE_*
+_linear_half_lib = None
+
+
+def linear_half_library_path() -> str:
+    return _LINEAR_HALF_LIB_PATH
+
+
+def _declare_linear_half(handle):
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    handle.lsq_linear_half_abi_version.restype = i32
+    handle.lsq_linear_half_abi_version.argtypes = []
+    handle.lsq_linear_signw_half_workspace_bytes.restype = i64
+    handle.lsq_linear_signw_half_workspace_bytes.argtypes = [i64, i64, i32, i32]
+    handle.lsq_linear_signw_half.restype = i32
+    handle.lsq_linear_signw_half.argtypes = [vp, i32, f32, vp, i32, vp, vp, i64, i64, i64, vp, i32, vp, ctypes.c_size_t, vp]
+
+
+def linear_half_lib():
+    """Load (once) and return the 16-bit-activation linear-layer library; raises if it has not been built (no fallback, as
+    ``lib()``)."""
+    global _linear_half_lib
+    if _linear_half_lib is None:
+        _linear_half_lib = _load(_LINEAR_HALF_LIB_PATH, 'csrc/linear_half', _declare_linear_half,
+                                 'lsq_linear_half_abi_version', LINEAR_HALF_ABI_VERSION, 'liblsq_hip_linear_half.so')
+    return _linear_half_lib
+
+
+_linear_half_ws_cache = {}
+
+
+def linear_signw_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: torch.Tensor, bias: Optional[torch.Tensor],
+                      M: int, F: int, O: int, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """y [M, O] = F.linear(x.clamp(-alpha, alpha), w_q, bias) for bf16 / fp16 rows ``x`` [M, F] (any 2-byte-aligned data
+    pointer) and the sign planes ``wbits`` / fp32 scales ``wscales`` [kw, O] lsq_pack_weight took and wrote for (O, F, 1, 1)
+    (lsq_linear_signw_half); ``alpha`` is the symmetric clamp bound (rounded into x's type, as Tensor.clamp rounds it),
+    negative for none.  ``out_dtype``: x.dtype (the default) or torch.float32; the 16-bit result is the fp32 one rounded
+    once.  The fp32 running sum of a 16-bit result of more than two planes lives in a workspace cached per
+    (device, stream) like the solver's (rewritten by every call; kernels of one stream run in order)."""
+    M, F, O = int(M), int(F), int(O)
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f'lsq_linear_signw_half: x must be a bfloat16 or float16 tensor, got {x.dtype}')
+    if out_dtype not in (torch.float32, x.dtype):
+        raise TypeError(f'lsq_linear_signw_half: out_dtype must be torch.float32 or {x.dtype}, got {out_dtype}')
+    _check_linear('lsq_linear_signw_half', {'M': M, 'F': F, 'O': O}, {'wscales': wscales}, {'wbits': wbits},
+                  bad=x.numel() != M * F, wplanes=(wbits, wscales, F, O), bias=bias)
+    dev = wscales.device
+    if not x.is_contiguous():
+        raise ValueError('lsq_linear_signw_half: operands must be contiguous')
+    if x.device != dev:
+        raise ValueError('lsq_linear_signw_half: every operand on the same cuda device')
+    kw, nw, opad = wscales.shape[0], (F + 63) // 64, (O + 15) // 16 * 16
+    hl = linear_half_lib()
+    xdt, ydt = LINEAR_HALF_DTYPES[x.dtype], LINEAR_HALF_DTYPES[out_dtype]
+    need = int(hl.lsq_linear_signw_half_workspace_bytes(M, O, kw, ydt))
+    ws = _stream_buffer(_linear_half_ws_cache, need, dev) if need else None
+    y = torch.empty((M, O), dtype=out_dtype, device=dev)
+    launches = (kw + 1) // 2                         # (the fp32 sum is read back by every launch after the first)
+    with _on(y), _Timed('lsq_linear_signw_half', 2 * M * F * launches + 8 * kw * nw * opad + 8 * M * O * (launches - 1)
+                        + y.element_size() * M * O, 2 * M * F * O * kw):      # 16-bit FLOPs: one pass per plane
+        check(hl.lsq_linear_signw_half(x.data_ptr(), xdt, float(alpha), wbits.data_ptr(), kw, wscales.data_ptr(), ptr(bias),
+                                       M, F, O, y.data_ptr(), ydt, ptr(ws), 0 if ws is None else ws.numel(),
+                                       stream_ptr(dev)), 'lsq_linear_signw_half')
+    return y
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

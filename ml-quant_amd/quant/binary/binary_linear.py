@@ -18,12 +18,18 @@ Dispatch of ``forward``:
   * the same conditions with ``fp`` activations and binary weights (any T and F) -> the weight sign planes packed once per
     ``eval()`` session, then lsq_linear_signw (liblsq_hip_linear_fp.so): the clamp fused, the fp32 rows split into bf16
     hi + lo on the bf16 matrix cores.  No fallback on this branch either.
+  * the same conditions with ``fp`` activations, binary fp32 weights and a bf16 / fp16 input, autocast off or set to the
+    input's own type -> the same packed planes, then lsq_linear_signw_half (liblsq_hip_linear_half.so): the 16-bit rows
+    read as they are, one MFMA per k-step, the output in the input's type (the fp32 result rounded once).  On a shape
+    class of ``half_kernel_classes``' complement the rows go through ``x.float()`` -> lsq_linear_signw -> ``.to(dtype)``
+    instead.  No fallback on this branch either.
   * CUDA fp32 tensor in ``train()`` mode with ``hip_train`` set (class attribute, False by default), binary weights and
     the same limits -> the kernels of the inference path for the forward and ``quant.binary.hip_train_linear`` for the
     backward (lsq_linear_signw_dgrad of liblsq_hip_linear_train.so, straight-through estimator), one
     ``torch.autograd.Function`` per call.
-  * anything else (CPU, training without ``hip_train``, ``fp`` weights, F % 64 != 0 with T > 1 for binary activations,
-    beyond the kernels' limits) -> the torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on
+  * anything else (CPU, training without ``hip_train``, ``fp`` weights, 16-bit weights, a 16-bit input with binary
+    activations or under an autocast of another type, F % 64 != 0 with T > 1 for binary activations, beyond the kernels'
+    limits) -> the torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on
     the same 4-D views.
 """
 
@@ -48,6 +54,11 @@ class QuantLinear(HipQuantModule, nn.Linear):
     #: train-mode CUDA tensors through the kernels (quant.binary.hip_train_linear).  False: the torch formulation, the
     #: default until the measured train step says otherwise
     hip_train = False
+
+    #: shape classes of lsq_linear_signw's tile rule ('split': fewer than 256 tiles of 64 x 64 in M x O, 'big': at least 256
+    #: tiles of 128 x 128, 'small': between them) on which a bf16 / fp16 input takes lsq_linear_signw_half -- those where it
+    #: is measured faster than x.float() -> lsq_linear_signw -> .to(dtype), the route the other classes take
+    half_kernel_classes = frozenset(('split', 'small', 'big'))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
@@ -84,13 +95,17 @@ class QuantLinear(HipQuantModule, nn.Linear):
             return False
         if x.dim() < 2 or x.shape[-1] != self.in_features or x.numel() == 0:
             return False
+        if x.dtype != torch.float32 and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') != x.dtype:
+            return False                  # (a 16-bit input under an autocast of another type: torch decides the types)
         return self._hip_supports(x)
 
     def _hip_supports(self, x: torch.Tensor) -> bool:
-        """The limits of lsq_act_quant and lsq_linear_xnor (binary activations) or of lsq_linear_signw (fp activations);
-        anything outside them takes the torch formulation."""
+        """The limits of lsq_act_quant and lsq_linear_xnor (binary activations, fp32) or of lsq_linear_signw /
+        lsq_linear_signw_half (fp activations, fp32 / bf16 and fp16); anything outside them takes the torch formulation."""
         from quant import _hip
-        if x.dtype != torch.float32 or self.weight.dtype != torch.float32:
+        if self.weight.dtype != torch.float32:
+            return False
+        if x.dtype != torch.float32 and (self.x_quant != 'fp' or x.dtype not in (torch.bfloat16, torch.float16)):
             return False
         if self.x_quant == 'fp':
             n, t = self._rows(x)
@@ -125,6 +140,13 @@ class QuantLinear(HipQuantModule, nn.Linear):
             self._hip_cache['w'] = hit
         return hit[1], hit[2], hit[3]
 
+    @staticmethod
+    def _tile_class(m: int, o: int) -> str:
+        """The kernel lsq_linear_signw and lsq_linear_signw_half run for m rows and o outputs (their tile rule)."""
+        if ((m + 63) // 64) * ((o + 63) // 64) < 256:
+            return 'split'
+        return 'big' if ((m + 127) // 128) * ((o + 127) // 128) >= 256 else 'small'
+
     def _forward_hip(self, x: torch.Tensor) -> torch.Tensor:
         from quant import _hip
         x = x.detach()
@@ -134,7 +156,16 @@ class QuantLinear(HipQuantModule, nn.Linear):
         bias = None if self.bias is None else self.bias.detach()
         if self.x_quant == 'fp':
             # (the kernel reads whole rows: a strided input -- h[:, 0], a slice of a wider tensor -- is copied first)
-            y = _hip.linear_signw(x.reshape(n * t, f).contiguous(), self._alpha(), wbits, wscales, bias, n * t, f, o)
+            rows = x.reshape(n * t, f).contiguous()
+            if x.dtype == torch.float32:
+                y = _hip.linear_signw(rows, self._alpha(), wbits, wscales, bias, n * t, f, o)
+            elif self._tile_class(n * t, o) in self.half_kernel_classes:
+                y = _hip.linear_signw_half(rows, self._alpha(), wbits, wscales, bias, n * t, f, o)
+            else:
+                # the clamp bound as Tensor.clamp would round it into x's type (negative: none)
+                alpha = self._alpha()
+                alpha = float(torch.tensor(alpha, dtype=x.dtype)) if alpha >= 0 else alpha
+                y = _hip.linear_signw(rows.float(), alpha, wbits, wscales, bias, n * t, f, o).to(x.dtype)
             return y.view(*x.shape[:-1], o)
         geom = _hip.make_geom(n, t * f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
         k = self.x_approximate.n_planes
