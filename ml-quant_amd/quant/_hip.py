@@ -990,6 +990,71 @@ def linear_signw_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscale
     return y
 
 
+# ---- the 16-bit activation quantizer library (include/lsq_hip_linear_act_half.h): an eighth shared object, loaded on first use
+_LINEAR_ACT_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_act_half.so')
+LINEAR_ACT_HALF_ABI_VERSION = 1
+_linear_act_half_lib = None
+
+
+def linear_act_half_library_path() -> str:
+    return _LINEAR_ACT_HALF_LIB_PATH
+
+
+def _declare_linear_act_half(handle):
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    handle.lsq_linear_act_half_abi_version.restype = i32
+    handle.lsq_linear_act_half_abi_version.argtypes = []
+    handle.lsq_linear_act_quant_half.restype = i32
+    handle.lsq_linear_act_quant_half.argtypes = [vp, i32, i64, i64, i32, i32, f32, vp, vp, vp, vp]
+
+
+def linear_act_half_lib():
+    """Load (once) and return the 16-bit activation quantizer library; raises if it has not been built (no fallback, as
+    ``lib()``)."""
+    global _linear_act_half_lib
+    if _linear_act_half_lib is None:
+        _linear_act_half_lib = _load(_LINEAR_ACT_HALF_LIB_PATH, 'csrc/linear_act_half', _declare_linear_act_half,
+                                     'lsq_linear_act_half_abi_version', LINEAR_ACT_HALF_ABI_VERSION,
+                                     'liblsq_hip_linear_act_half.so')
+    return _linear_act_half_lib
+
+
+def linear_act_quant_half(x: torch.Tensor, scheme: int, k: int, alpha: float, planes: torch.Tensor, scales: torch.Tensor,
+                          forced: Optional[torch.Tensor] = None) -> None:
+    """Sign planes and scales of the bf16 / fp16 rows ``x`` [N, L] (any 2-byte-aligned data pointer) into ``planes`` (int64,
+    at least k * N * ceil(L / 64) words: what lsq_act_quant writes for (N, L, 1, 1), every word written in full) and
+    ``scales`` [k, N] fp32 (lsq_linear_act_quant_half).  ``alpha`` is the symmetric clamp bound ALREADY ROUNDED into x's type
+    (as Tensor.clamp rounds it), negative for none; ``forced`` [k, N] fp32: scales to use instead of computing them --
+    required for ls-2 / ls-T, whose free-running solve is lsq_act_quant's."""
+    scheme, k = int(scheme), int(k)
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f'lsq_linear_act_quant_half: x must be a bfloat16 or float16 tensor, got {x.dtype}')
+    fp32 = {'scales': scales} if forced is None else {'scales': scales, 'forced': forced}
+    for dtype, named in ((torch.float32, fp32), (torch.int64, {'planes': planes})):
+        wrong = [name for name, t in named.items() if t.dtype != dtype]
+        if wrong:
+            raise TypeError(f'lsq_linear_act_quant_half: {", ".join(wrong)} must be {dtype} tensors')
+    tensors = [x, planes, *fp32.values()]
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError('lsq_linear_act_quant_half: operands must be contiguous')
+    if x.dim() != 2 or x.numel() == 0 or k < 1:
+        raise ValueError(f'lsq_linear_act_quant_half: bad sizes k={k} for x of shape {tuple(x.shape)}')
+    N, L = x.shape
+    if planes.numel() < k * N * ((L + 63) // 64) or any(tuple(t.shape) != (k, N) for t in fp32.values()):
+        raise ValueError('lsq_linear_act_quant_half: activation planes / scales and (k, N, L) do not match')
+    if scheme in (SCHEME_LS2, SCHEME_LST) and forced is None:
+        raise ValueError('lsq_linear_act_quant_half: ls-2 / ls-T need forced scales (their solve reads fp32 rows: lsq_act_quant)')
+    dev = x.device
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError('lsq_linear_act_quant_half: every operand on the same cuda device')
+    passes = 1 if forced is not None else k
+    with _on(x), (_Timed('lsq_linear_act_quant_half', N * (2 * L * passes + k * ((L + 63) // 64) * 8), 0)
+                  if _timing is not None else _UNTIMED):
+        check(linear_act_half_lib().lsq_linear_act_quant_half(
+            x.data_ptr(), LINEAR_HALF_DTYPES[x.dtype], N, L, scheme, k, float(alpha), ptr(forced), planes.data_ptr(),
+            scales.data_ptr(), stream_ptr(dev)), 'lsq_linear_act_quant_half')
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

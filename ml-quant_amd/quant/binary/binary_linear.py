@@ -23,12 +23,19 @@ Dispatch of ``forward``:
     read as they are, one MFMA per k-step, the output in the input's type (the fp32 result rounded once).  On a shape
     class of ``half_kernel_classes``' complement the rows go through ``x.float()`` -> lsq_linear_signw -> ``.to(dtype)``
     instead.  No fallback on this branch either.
+  * the conditions of the first branch with a bf16 / fp16 input, fp32 weights, autocast off or set to the input's own type,
+    and activations that need no scale solve -- ``ls-1``, ``gf-k``, or any scheme whose scales are given
+    (``x_approximate.eval_scales``: a moving average, ``_forced_scales``) -> lsq_linear_act_quant_half
+    (liblsq_hip_linear_act_half.so) reads the 16-bit rows as they are (the clamp bound rounded into their type), then
+    lsq_linear_xnor as above; the output is its fp32 result rounded once into the input's type.  With
+    ``act_half_kernel = False`` the rows go through ``x.float()`` -> lsq_act_quant instead: the same bits.  No
+    fallback on this branch either.
   * CUDA fp32 tensor in ``train()`` mode with ``hip_train`` set (class attribute, False by default), binary weights and
     the same limits -> the kernels of the inference path for the forward and ``quant.binary.hip_train_linear`` for the
     backward (lsq_linear_signw_dgrad of liblsq_hip_linear_train.so, straight-through estimator), one
     ``torch.autograd.Function`` per call.
-  * anything else (CPU, training without ``hip_train``, ``fp`` weights, 16-bit weights, a 16-bit input with binary
-    activations or under an autocast of another type, F % 64 != 0 with T > 1 for binary activations, beyond the kernels'
+  * anything else (CPU, training without ``hip_train``, ``fp`` weights, 16-bit weights, a 16-bit input with free-running
+    ``ls-2`` / ``ls-T`` activations or under an autocast of another type, F % 64 != 0 with T > 1 for binary activations, beyond the kernels'
     limits) -> the torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on
     the same 4-D views.
 """
@@ -59,6 +66,10 @@ class QuantLinear(HipQuantModule, nn.Linear):
     #: tiles of 128 x 128, 'small': between them) on which a bf16 / fp16 input takes lsq_linear_signw_half -- those where it
     #: is measured faster than x.float() -> lsq_linear_signw -> .to(dtype), the route the other classes take
     half_kernel_classes = frozenset(('split', 'small', 'big'))
+
+    #: a bf16 / fp16 input with binary activations is quantized by lsq_linear_act_quant_half (True) or, for the comparison
+    #: of DESIGN 4.16, by lsq_act_quant on x.float() (False): the same planes, scales and output bits
+    act_half_kernel = True
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
@@ -100,12 +111,13 @@ class QuantLinear(HipQuantModule, nn.Linear):
         return self._hip_supports(x)
 
     def _hip_supports(self, x: torch.Tensor) -> bool:
-        """The limits of lsq_act_quant and lsq_linear_xnor (binary activations, fp32) or of lsq_linear_signw /
-        lsq_linear_signw_half (fp activations, fp32 / bf16 and fp16); anything outside them takes the torch formulation."""
+        """The limits of lsq_act_quant / lsq_linear_act_quant_half and lsq_linear_xnor (binary activations, fp32 / bf16 and
+        fp16) or of lsq_linear_signw / lsq_linear_signw_half (fp activations, fp32 / bf16 and fp16); anything outside them
+        takes the torch formulation."""
         from quant import _hip
         if self.weight.dtype != torch.float32:
             return False
-        if x.dtype != torch.float32 and (self.x_quant != 'fp' or x.dtype not in (torch.bfloat16, torch.float16)):
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
             return False
         if self.x_quant == 'fp':
             n, t = self._rows(x)
@@ -121,6 +133,8 @@ class QuantLinear(HipQuantModule, nn.Linear):
             return False
         if self.x_quant in ('ls-2', 'ls-T') and (row + self.act_skip - 1) // self.act_skip >= _hip.MAX_SOLVER_KEYS:
             return False
+        if x.dtype != torch.float32 and self.x_quant in ('ls-2', 'ls-T') and self.x_approximate.eval_scales(n) is None:
+            return False                  # (the free-running scale solve reads fp32 rows)
         return True
 
     # ------------------------------------------------------------------ HIP path
@@ -163,13 +177,18 @@ class QuantLinear(HipQuantModule, nn.Linear):
                 y = _hip.linear_signw_half(rows, self._alpha(), wbits, wscales, bias, n * t, f, o)
             else:
                 # the clamp bound as Tensor.clamp would round it into x's type (negative: none)
-                alpha = self._alpha()
-                alpha = float(torch.tensor(alpha, dtype=x.dtype)) if alpha >= 0 else alpha
-                y = _hip.linear_signw(rows.float(), alpha, wbits, wscales, bias, n * t, f, o).to(x.dtype)
+                y = _hip.linear_signw(rows.float(), self._alpha_in(x.dtype), wbits, wscales, bias, n * t, f, o).to(x.dtype)
             return y.view(*x.shape[:-1], o)
         geom = _hip.make_geom(n, t * f, 1, 1, o, 1, 1, (1, 1), (0, 0), (1, 1), 1)
         k = self.x_approximate.n_planes
-        planes, scales = self._act_planes(x.reshape(n, t * f), geom, k, _hip)
+        if x.dtype == torch.float32:
+            planes, scales = self._act_planes(x.reshape(n, t * f), geom, k, _hip)
+        else:
+            # 16-bit rows: the bound as Tensor.clamp would round it into x's type; planes and scales in a workspace of their
+            # own per type; the cast route of DESIGN 4.16 feeds the same rows to lsq_act_quant as fp32
+            rows = x.reshape(n, t * f).contiguous()
+            planes, scales = self._act_planes(rows if self.act_half_kernel else rows.float(), geom, k, _hip, extra=(x.dtype,),
+                                              alpha=self._alpha_in(x.dtype))
         y = _hip.linear_xnor(planes, k, scales, t, wbits, wsum, wscales, bias, n * t, f, o)
         self.last_act_scales = scales
-        return y.view(*x.shape[:-1], o)
+        return (y if x.dtype == torch.float32 else y.to(x.dtype)).view(*x.shape[:-1], o)

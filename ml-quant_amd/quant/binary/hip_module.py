@@ -100,6 +100,11 @@ class HipQuantModule:
             return float(self.clamp_config.get('alpha', 2))
         return -1.0
 
+    def _alpha_in(self, dtype: torch.dtype) -> float:
+        """``_alpha()`` as ``Tensor.clamp`` rounds it into a tensor of ``dtype`` (bf16: 1.3 -> 1.296875); -1 stays -1."""
+        alpha = self._alpha()
+        return float(torch.tensor(alpha, dtype=dtype)) if alpha >= 0 else alpha
+
     # ------------------------------------------------------------------ invalidation of the derived state
     def _replicate_for_data_parallel(self):
         replica = super()._replicate_for_data_parallel()
@@ -134,10 +139,11 @@ class HipQuantModule:
             self._hip_cache[key] = ws
         return ws
 
-    def _act_planes(self, x, geom, k, _hip, extra: tuple = (), pre=None):
-        """Quantize ``x`` (the samples of ``geom``) with lsq_act_quant into this module's plane workspace of kind ``'act'``;
-        returns (planes, scales).  ``extra``: what the caller's plane layout depends on beyond ``geom``'s N, C, H, W;
-        ``pre``: a folded batch norm for the read."""
+    def _act_planes(self, x, geom, k, _hip, extra: tuple = (), pre=None, alpha: Optional[float] = None):
+        """Quantize ``x`` (the samples of ``geom``) with lsq_act_quant -- bf16 / fp16 rows [N, L] of a geometry (N, L, 1, 1):
+        with lsq_linear_act_quant_half -- into this module's plane workspace of kind ``'act'``; returns (planes, scales).
+        ``extra``: what the caller's plane layout depends on beyond ``geom``'s N, C, H, W; ``pre``: a folded batch norm for the
+        read; ``alpha``: the clamp bound where it is not ``_alpha()`` (rounded into a 16-bit type)."""
         shape, device = geom.key()[:4], x.device
         n = shape[0]
         planes, scales = self._workspace(
@@ -147,5 +153,9 @@ class HipQuantModule:
         forced = xq.eval_scales(n)
         if forced is not None:
             forced = forced.to(device=device, dtype=torch.float32).contiguous()
-        _hip.act_quant(x, geom, xq.hip_scheme, k, self.act_skip, self._alpha(), planes, scales, forced, pre)
+        alpha = self._alpha() if alpha is None else alpha
+        if x.dtype == torch.float32:
+            _hip.act_quant(x, geom, xq.hip_scheme, k, self.act_skip, alpha, planes, scales, forced, pre)
+        else:
+            _hip.linear_act_quant_half(x, xq.hip_scheme, k, alpha, planes, scales, forced)
         return planes, scales
