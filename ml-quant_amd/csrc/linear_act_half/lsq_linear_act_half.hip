@@ -25,8 +25,11 @@
 #include <algorithm>
 
 #include "lsq_hip_linear_act_half.h"
+#include "../lsq_half_rows.h"
 
 namespace {
+
+using namespace lsq_half;                             // to_f32, clamp_sym, load_group, wave_sum
 
 constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kWaveRowMax = 4096;                     // elements: longer rows take a workgroup each
@@ -46,30 +49,6 @@ struct Args {
   int nw, k;
   float alpha;                        // clamp bound (negative: none)
 };
-
-template <bool F16>
-__device__ __forceinline__ float to_f32(unsigned h) {  // h: 16 bits
-  if constexpr (F16) return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
-  else return __uint_as_float(h << 16);
-}
-
-__device__ __forceinline__ float clamp_sym(float x, float alpha) {
-  return alpha >= 0.f ? fminf(fmaxf(x, -alpha), alpha) : x;
-}
-
-// group g of the row (g inside the row's groups): the raw 16 bytes; what lies past L is unspecified (masked by the caller)
-template <bool VEC>
-__device__ __forceinline__ uint4 load_group(const unsigned short* xrow, long long L, int g) {
-  const long long e = 8ll * g;
-  if constexpr (VEC) {                                // L % 8 == 0: a group is inside the row or past it
-    return *reinterpret_cast<const uint4*>(xrow + (e < L ? e : L - 8));
-  } else {
-    unsigned h[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = xrow[e + j < L ? e + j : L - 1];
-    return make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
-  }
-}
 
 // One row by T threads (t = the thread's index among them).  reduce(acc, q): the sum of acc over the T threads, the same
 // value in every thread.  stash: the threads' LDS room for `stash_groups` groups (kPasses only).
@@ -162,12 +141,6 @@ __device__ __forceinline__ void quant_row(const Args& a, long long row, int t, u
       if (t == 0) a.scales[q * a.N + row] = vq;
     }
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {  // xor butterfly: every lane ends with the same bits
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
 }
 
 template <bool F16, bool VEC, int MODE>

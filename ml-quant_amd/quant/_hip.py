@@ -1055,6 +1055,73 @@ def linear_act_quant_half(x: torch.Tensor, scheme: int, k: int, alpha: float, pl
             scales.data_ptr(), stream_ptr(dev)), 'lsq_linear_act_quant_half')
 
 
+# ---- the 16-bit free-running ls-2 / ls-T quantizer library (include/lsq_hip_linear_act_solve.h): a ninth shared object,
+# loaded on first use
+_LINEAR_ACT_SOLVE_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_act_solve.so')
+LINEAR_ACT_SOLVE_ABI_VERSION = 1
+_linear_act_solve_lib = None
+
+
+def linear_act_solve_library_path() -> str:
+    return _LINEAR_ACT_SOLVE_LIB_PATH
+
+
+def _declare_linear_act_solve(handle):
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    handle.lsq_linear_act_solve_abi_version.restype = i32
+    handle.lsq_linear_act_solve_abi_version.argtypes = []
+    handle.lsq_linear_act_quant_solve_half.restype = i32
+    handle.lsq_linear_act_quant_solve_half.argtypes = [vp, i32, i64, i64, i32, i32, f32, vp, vp, vp, vp]
+
+
+def linear_act_solve_lib():
+    """Load (once) and return the 16-bit free-running ls-2 / ls-T quantizer library; raises if it has not been built (no
+    fallback, as ``lib()``)."""
+    global _linear_act_solve_lib
+    if _linear_act_solve_lib is None:
+        _linear_act_solve_lib = _load(_LINEAR_ACT_SOLVE_LIB_PATH, 'csrc/linear_act_solve', _declare_linear_act_solve,
+                                      'lsq_linear_act_solve_abi_version', LINEAR_ACT_SOLVE_ABI_VERSION,
+                                      'liblsq_hip_linear_act_solve.so')
+    return _linear_act_solve_lib
+
+
+def linear_act_quant_solve_half(x: torch.Tensor, scheme: int, skip: int, alpha: float, planes: torch.Tensor,
+                                scales: torch.Tensor, status: Optional[torch.Tensor] = None) -> None:
+    """Free-running ls-2 / ls-T on the bf16 / fp16 rows ``x`` [N, L] (any 2-byte-aligned data pointer): the optimal v1 of the
+    sub-sample ``row[::skip]``, v2 and both sign planes into ``planes`` (int64, at least 2 * N * ceil(L / 64) words: what
+    lsq_act_quant writes for (N, L, 1, 1), every word written in full), ``scales`` [2, N] fp32 and, where given, ``status`` [N]
+    int32 (1 = the row had a candidate) (lsq_linear_act_quant_solve_half).  ``alpha`` is the symmetric clamp bound ALREADY
+    ROUNDED into x's type (as Tensor.clamp rounds it), negative for none."""
+    scheme, skip = int(scheme), int(skip)
+    what = 'lsq_linear_act_quant_solve_half'
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f'{what}: x must be a bfloat16 or float16 tensor, got {x.dtype}')
+    if scheme not in (SCHEME_LS2, SCHEME_LST):
+        raise ValueError(f'{what}: the scheme must be ls-2 or ls-T, got {scheme}')
+    named = ((torch.float32, {'scales': scales}), (torch.int64, {'planes': planes}),
+             (torch.int32, {} if status is None else {'status': status}))
+    for dtype, group in named:
+        wrong = [name for name, t in group.items() if t.dtype != dtype]
+        if wrong:
+            raise TypeError(f'{what}: {", ".join(wrong)} must be {dtype} tensors')
+    tensors = [x, planes, scales] + ([] if status is None else [status])
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: operands must be contiguous')
+    if x.dim() != 2 or x.numel() == 0 or skip < 1:
+        raise ValueError(f'{what}: bad sizes skip={skip} for x of shape {tuple(x.shape)}')
+    N, L = x.shape
+    if (planes.numel() < 2 * N * ((L + 63) // 64) or tuple(scales.shape) != (2, N)
+            or (status is not None and tuple(status.shape) != (N,))):
+        raise ValueError(f'{what}: activation planes / scales / status and (N, L) do not match')
+    dev = x.device
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError(f'{what}: every operand on the same cuda device')
+    with _on(x), (_Timed(what, N * (2 * L * 2 + 2 * ((L + 63) // 64) * 8), 0) if _timing is not None else _UNTIMED):
+        check(linear_act_solve_lib().lsq_linear_act_quant_solve_half(
+            x.data_ptr(), LINEAR_HALF_DTYPES[x.dtype], N, L, scheme, skip, float(alpha), planes.data_ptr(), scales.data_ptr(),
+            ptr(status), stream_ptr(dev)), what)
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

@@ -30,12 +30,17 @@ Dispatch of ``forward``:
     lsq_linear_xnor as above; the output is its fp32 result rounded once into the input's type.  With
     ``act_half_kernel = False`` the rows go through ``x.float()`` -> lsq_act_quant instead: the same bits.  No
     fallback on this branch either.
+  * the conditions of the branch above with free-running ``ls-2`` / ``ls-T`` activations and ``act_half_solve`` set (class
+    attribute, False by default: nothing is measured yet) -> lsq_linear_act_quant_solve_half
+    (liblsq_hip_linear_act_solve.so): the v1 solve on a table of one count per 15-bit magnitude, v2 and both planes in one
+    launch, then lsq_linear_xnor; v1 and the planes are those of lsq_act_quant on ``x.float()``, which is the route
+    ``act_half_kernel = False`` takes.  No fallback on this branch either.
   * CUDA fp32 tensor in ``train()`` mode with ``hip_train`` set (class attribute, False by default), binary weights and
     the same limits -> the kernels of the inference path for the forward and ``quant.binary.hip_train_linear`` for the
     backward (lsq_linear_signw_dgrad of liblsq_hip_linear_train.so, straight-through estimator), one
     ``torch.autograd.Function`` per call.
   * anything else (CPU, training without ``hip_train``, ``fp`` weights, 16-bit weights, a 16-bit input with free-running
-    ``ls-2`` / ``ls-T`` activations or under an autocast of another type, F % 64 != 0 with T > 1 for binary activations, beyond the kernels'
+    ``ls-2`` / ``ls-T`` activations without ``act_half_solve`` or under an autocast of another type, F % 64 != 0 with T > 1 for binary activations, beyond the kernels'
     limits) -> the torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on
     the same 4-D views.
 """
@@ -70,6 +75,11 @@ class QuantLinear(HipQuantModule, nn.Linear):
     #: a bf16 / fp16 input with binary activations is quantized by lsq_linear_act_quant_half (True) or, for the comparison
     #: of DESIGN 4.16, by lsq_act_quant on x.float() (False): the same planes, scales and output bits
     act_half_kernel = True
+
+    #: a bf16 / fp16 input with FREE-RUNNING ls-2 / ls-T activations takes lsq_linear_act_quant_solve_half (with
+    #: act_half_kernel = False: lsq_act_quant on x.float(), the same v1 and planes).  False: the torch formulation, the
+    #: default until the kernel is measured against the cast route
+    act_half_solve = False
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
@@ -111,7 +121,7 @@ class QuantLinear(HipQuantModule, nn.Linear):
         return self._hip_supports(x)
 
     def _hip_supports(self, x: torch.Tensor) -> bool:
-        """The limits of lsq_act_quant / lsq_linear_act_quant_half and lsq_linear_xnor (binary activations, fp32 / bf16 and
+        """The limits of lsq_act_quant / lsq_linear_act_quant_half / lsq_linear_act_quant_solve_half and lsq_linear_xnor (binary activations, fp32 / bf16 and
         fp16) or of lsq_linear_signw / lsq_linear_signw_half (fp activations, fp32 / bf16 and fp16); anything outside them
         takes the torch formulation."""
         from quant import _hip
@@ -133,8 +143,9 @@ class QuantLinear(HipQuantModule, nn.Linear):
             return False
         if self.x_quant in ('ls-2', 'ls-T') and (row + self.act_skip - 1) // self.act_skip >= _hip.MAX_SOLVER_KEYS:
             return False
-        if x.dtype != torch.float32 and self.x_quant in ('ls-2', 'ls-T') and self.x_approximate.eval_scales(n) is None:
-            return False                  # (the free-running scale solve reads fp32 rows)
+        if (x.dtype != torch.float32 and self.x_quant in ('ls-2', 'ls-T') and not self.act_half_solve
+                and self.x_approximate.eval_scales(n) is None):
+            return False                  # (the free-running 16-bit scale solve is off by default: DESIGN 4.17)
         return True
 
     # ------------------------------------------------------------------ HIP path
