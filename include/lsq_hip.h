@@ -141,12 +141,18 @@ int lsq_solve_rows(const float* rows, int64_t R, int64_t M, int skip, int ternar
  *   next        NULL, or where the epilogue leaves the next layer's input: sign(clamp(y * pre_scale[o] + pre_shift[o]))
  *               as plane words [N][O/64][Ho + 2 pad_h][Wo + 2 pad_w] (halo pre-zeroed by the caller, interior fully
  *               written) and, ADDED to sum_units[N] (int64, zeroed by the caller before the launch), the row sums of
- *               |clamp(.)| in units of 2^e, e = ceil(log2 clamp_alpha) - 31 -- the exact arithmetic of lsq_act_quant's
+ *               |clamp(.)| in units of 2^e, e = e2 - 31 with clamp_alpha = m 2^e2, 0.5 <= m < 1 (frexpf: 2^e2 >= alpha >
+ *               2^(e2-1), and 2^e2 = 2 alpha when alpha is a power of two) -- the exact arithmetic of lsq_act_quant's
  *               plain sweeps, so that float(sum_units * 2^e / (O Ho Wo)) IS the scale lsq_act_quant(LS1) would return
  *   x_units     NULL (then xscales [1][N] as in lsq_xnor_conv2d), or the sum_units a previous call left for THIS layer's
  *               input; x_alpha = this layer's clamp (> 0), which fixes the unit
  * One activation plane; 3x3 kernels over 64 / 128 / 256 / 512 channels (the integer-MFMA kernel), O a multiple of 64 when
  * next is given; LSQ_E_UNSUPPORTED otherwise (the caller takes lsq_act_quant + lsq_xnor_conv2d: same bits).
+ * Row limit: lsq_act_quant forms a row's sum in this exact arithmetic only for rows of at most 2^22 elements, so the chain
+ * call returns LSQ_E_UNSUPPORTED, before any launch, when next is given and O * Ho * Wo > 2^22 (the consumer's row) or
+ * x_units is given and C * H * W > 2^22: beyond that the units would not be the scale the separate launch returns.
+ * Both x_units and xscales given: LSQ_E_SCHEME;  next with NULL planes / sum_units, or only one of pre_scale / pre_shift:
+ * LSQ_E_NULL.  A refused call writes nothing.
  */
 typedef struct {
   uint64_t* planes;

@@ -390,9 +390,11 @@ __device__ __forceinline__ void sweep_row(const Args& a, const float* __restrict
 
 // EXACT (plain sweeps under a clamp): the row sum is the same NUMBER however the row's elements are dealt to lanes and
 // workgroups -- whatever the batch size, lane sharing or row split.  The fp32 sum of every group of 8 channels (fixed
-// membership and order) is rounded to a multiple of 2^e, e = ceil(log2 alpha) - 31 (|x| <= alpha: a relative step of
-// 2^-32 of a typical group sum), and multiples of 2^e below 2^(53 + e) -- 4 million elements at the clamp -- add without
-// rounding in fp64.
+// membership and order) is rounded to a multiple of 2^e, e = e2 - 31 with alpha = m 2^e2, 0.5 <= m < 1 (frexpf: 2^e2 >=
+// alpha > 2^(e2-1); 2^e2 = 2 alpha when alpha is a power of two.  |x| <= alpha: a relative step of 2^-32 of a typical group
+// sum), and multiples of 2^e below 2^(53 + e) -- 4 million elements at the clamp -- add without rounding in fp64: rows of
+// at most 2^22 elements (run<VEC>, where qmagic is set); longer rows take the plain fp64 sum, and lsq_xnor_conv2d_chain,
+// whose epilogue is always exact, refuses to stand in for them (include/lsq_hip.h).
 template <int VEC, bool HIST, int QM, bool SPLIT, bool EXACT, class L>
 __device__ __forceinline__ PassOut pack_pass(const Args& a, L* lds, const float* __restrict__ xrow, unsigned long long* __restrict__ prow, int q) {
   // (a: the kernel's own argument block -- scalar registers; a copy staged through LDS cost a microsecond per launch)

@@ -27,6 +27,9 @@ namespace lsq {
 namespace {
 
 constexpr int kDefaultOT = 16;
+// chained 1-bit layers: the longest row whose sum lsq_act_quant's plain sweeps form exactly (lsq_act_quant.hip, where qmagic is
+// set); the chain epilogue is always exact, so only up to here are its units the scale lsq_act_quant would return
+constexpr long long kChainMaxRow = 1ll << 22;
 
 template <int KX, int OT>
 __global__ __launch_bounds__(256) void xnor_conv_kernel(ConvArgs a) {
@@ -290,6 +293,8 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
     if (kx != 1) return LSQ_E_SCHEME;
     if (x_units) {
       if (!(x_alpha > 0.f)) return LSQ_E_UNSUPPORTED;
+      // lsq_act_quant's sweeps sum exactly only up to kChainMaxRow elements per row: a longer row's units would not be ITS scale
+      if ((long long)g->C * g->H * g->W > kChainMaxRow) return LSQ_E_UNSUPPORTED;
       int e2 = 0;
       (void)frexpf(x_alpha, &e2);
       a.xunits = (const long long*)x_units;
@@ -300,6 +305,7 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
       if (!next->planes || !next->sum_units) return LSQ_E_NULL;
       if ((next->pre_scale == nullptr) != (next->pre_shift == nullptr)) return LSQ_E_NULL;
       if (!(next->clamp_alpha > 0.f) || g->O % 64 || next->pad_h < 0 || next->pad_w < 0) return LSQ_E_UNSUPPORTED;
+      if ((long long)g->O * Ho * Wo > kChainMaxRow) return LSQ_E_UNSUPPORTED;      // (the consumer's row: as above)
       int e2 = 0;
       (void)frexpf(next->clamp_alpha, &e2);
       a.nq_planes32 = (unsigned*)next->planes;

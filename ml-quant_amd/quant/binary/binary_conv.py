@@ -168,6 +168,8 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             return None
         if n * self.out_channels * ho * wo > chain.MAX_ELEMENTS:    # (large layers: the separate HBM-bound sweep is cheaper)
             return None
+        if self.out_channels * ho * wo > chain.MAX_ROW_ELEMENTS:    # (lsq_xnor_conv2d_chain refuses it: include/lsq_hip.h)
+            return None
         bn, conv = next_q
         if not isinstance(conv, QuantConv2d) or conv.x_quant != 'ls-1' or conv.training or conv.w_quant == 'fp':
             return None

@@ -24,6 +24,10 @@ ENABLED = True
 #: ResNet-18 ls-1, batch 256: chaining the 7 x 7 layers (6.4 M) 1.942 -> 1.956 ms, the 14 x 14 ones too (12.8 M) 1.991 ms,
 #: 28 x 28 too 2.081 ms, every layer 2.194 ms.
 MAX_ELEMENTS = 1 << 23
+#: a consumer ROW (one sample: channels x pixels) of more than this many elements is not chained: ``lsq_act_quant`` sums a row
+#: exactly only up to here, so beyond it the epilogue's exact row sum would not be the scale the separate launch returns
+#: (``lsq_xnor_conv2d_chain`` refuses such a call; at batch 1 or 2 ``MAX_ELEMENTS`` alone would let it through)
+MAX_ROW_ELEMENTS = 1 << 22
 
 _state = threading.local()
 _arenas = {}
