@@ -6,6 +6,7 @@ import torch
 
 import detgen
 from oracle import lsq_exact as E
+from train_step_cases import chain as _chain      # the quantizer chain in torch, shared with the train-step reference
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -110,28 +111,6 @@ def test_trace_is_off_by_default_and_after_the_block():
 
 
 # ------------------------------------------------------------------------------------------------ training
-def _chain(x, scales, alpha):
-    """The quantizer chain in torch: value and the straight-through gradient's closed form (tests/test_training.py pins
-    this formula to autograd through the reference-equal torch formulation)."""
-    inside = (x >= -alpha) & (x <= alpha) if alpha >= 0 else torch.ones_like(x, dtype=torch.bool)
-    c = x.clamp(-alpha, alpha) if alpha >= 0 else x
-    shape = (-1,) + (1,) * (x.dim() - 1)
-    r, d = torch.zeros_like(c), []
-    for v in scales:
-        di = c - r
-        d.append(di)
-        r = r + v.view(shape) * torch.where(di >= 0, 1.0, -1.0)
-
-    def grad(g):
-        G, acc = g.clone(), torch.zeros_like(g)
-        for v, di in zip(reversed(scales), reversed(d)):
-            t = torch.where(di.abs() <= 1, G * v.view(shape), torch.zeros_like(G))
-            acc = acc + t
-            G = G - t
-        return torch.where(inside, acc if len(scales) else g, torch.zeros_like(g))
-    return (r if len(scales) else c), grad
-
-
 @pytest.mark.parametrize('shape', [(5, 16, 6, 6), (3, 7, 5, 3), (24, 32, 3, 3), (2, 1, 1, 9)])
 @pytest.mark.parametrize('k', range(9))
 def test_ste_kernels_equal_the_torch_chain(shape, k):

@@ -58,7 +58,10 @@ def _check(g, g64, mag, what):
 
 
 def _geom(n, c, h, w, o, k, s, p):
-    return _hip().make_geom(n, c, h, w, o, k, k, (s, s), (p, p), (1, 1), 1)
+    """``k`` and ``p``: one number for both axes or (rows, columns)."""
+    kh, kw = k if isinstance(k, tuple) else (k, k)
+    ph, pw = p if isinstance(p, tuple) else (p, p)
+    return _hip().make_geom(n, c, h, w, o, kh, kw, (s, s), (ph, pw), (1, 1), 1)
 
 
 def _case_list():
@@ -88,6 +91,34 @@ def test_wgrad_equals_the_fp64_closed_form(c, o, n, h, w, k, s, p, scheme):
     planes, scales, kx = _planes(x, geom, scheme)
     g = hip.wgrad(planes, kx, scales, gy, geom)
     torch.cuda.synchronize()
+    g64, mag = _closed_form(_xq64(planes, scales, geom), gy, geom)
+    _check(g, g64, mag, (c, o, n, h, w, k, s, p, scheme))
+
+
+# kernels and paddings that differ between the axes: (C, O, N, H, W, (KH, KW), stride, (pad_h, pad_w), scheme)
+NON_SQUARE = [(20, 50, 3, 9, 8, (1, 3), 1, (0, 1), 'ls-2'),
+              (64, 33, 1, 8, 9, (3, 1), 1, (2, 0), 'ls-T'),
+              (20, 50, 2, 10, 11, (3, 5), 2, (2, 0), 'ls-2'),        # (H + 2p - k) odd on rows, even on columns
+              (16, 33, 2, 8, 8, (4, 3), 1, (3, 2), 'gf-3'),          # pad = k - 1 on both axes
+              (100, 96, 2, 8, 9, (2, 2), 2, (0, 1), 'ls-T'),         # even kernel, stride 2
+              (72, 8, 1, 20, 12, (8, 8), 1, (7, 0), 'ls-1'),         # the largest kernel: 64 taps
+              (130, 1, 3, 5, 4, (5, 2), 2, (1, 1), 'gf-8')]          # output 2 x 2, one out-channel
+
+
+@pytest.mark.parametrize('c,o,n,h,w,k,s,p,scheme', NON_SQUARE)
+def test_wgrad_at_non_square_kernels_and_per_axis_padding(c, o, n, h, w, k, s, p, scheme):
+    """The closed form reads KH, KW, pad_h and pad_w from the geometry: a kernel that swapped the axes, or took one padding for
+    both, would differ from it at every tap."""
+    hip = _hip()
+    geom = _geom(n, c, h, w, o, k, s, p)
+    ho, wo = hip.out_hw(geom)
+    assert ho >= 1 and wo >= 1
+    x = detgen.normal(f'wg.ns.x.{k}.{s}.{p}', (n, c, h, w), scale=1.3)
+    gy = detgen.normal(f'wg.ns.gy.{k}.{s}.{p}', (n, o, ho, wo), scale=1e-3).to(DEV)
+    planes, scales, kx = _planes(x, geom, scheme)
+    g = hip.wgrad(planes, kx, scales, gy, geom)
+    torch.cuda.synchronize()
+    assert tuple(g.shape) == (o, c) + k
     g64, mag = _closed_form(_xq64(planes, scales, geom), gy, geom)
     _check(g, g64, mag, (c, o, n, h, w, k, s, p, scheme))
 
