@@ -1122,6 +1122,77 @@ def linear_act_quant_solve_half(x: torch.Tensor, scheme: int, skip: int, alpha: 
             ptr(status), stream_ptr(dev)), what)
 
 
+# ---- the 16-bit activation quantizer of QuantConv2d (include/lsq_hip_conv_act_half.h): a tenth shared object, loaded on
+# first use
+_CONV_ACT_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_conv_act_half.so')
+CONV_ACT_HALF_ABI_VERSION = 1
+_conv_act_half_lib = None
+
+
+def conv_act_half_library_path() -> str:
+    return _CONV_ACT_HALF_LIB_PATH
+
+
+def _declare_conv_act_half(handle):
+    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    handle.lsq_conv_act_half_abi_version.restype = i32
+    handle.lsq_conv_act_half_abi_version.argtypes = []
+    handle.lsq_act_quant_half.restype = i32
+    handle.lsq_act_quant_half.argtypes = [vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
+
+
+def conv_act_half_lib():
+    """Load (once) and return the 16-bit convolution activation quantizer library; raises if it has not been built (no
+    fallback, as ``lib()``)."""
+    global _conv_act_half_lib
+    if _conv_act_half_lib is None:
+        _conv_act_half_lib = _load(_CONV_ACT_HALF_LIB_PATH, 'csrc/conv_act_half', _declare_conv_act_half,
+                                   'lsq_conv_act_half_abi_version', CONV_ACT_HALF_ABI_VERSION, 'liblsq_hip_conv_act_half.so')
+    return _conv_act_half_lib
+
+
+def act_quant_half(x: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: int, alpha: float, planes: torch.Tensor,
+                   scales: torch.Tensor, forced: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> None:
+    """Sign planes and scales of the bf16 / fp16 batch ``x`` [N, C, H, W] (contiguous, any 2-byte-aligned data pointer) of
+    ``geom`` into ``planes`` (int64, at least k * act_plane_words(geom) words in lsq_act_quant's layout, halo zeroed by the
+    caller, every interior word written in full), ``scales`` [k, N] fp32 and, where given, ``status`` [N] int32
+    (lsq_act_quant_half).  ``alpha`` is the symmetric clamp bound ALREADY ROUNDED into x's type (as Tensor.clamp rounds it),
+    negative for none; ``forced`` [k, N] fp32: scales to use instead of computing them; ``skip``: the sub-sampling stride of
+    the free-running ls-2 / ls-T solve."""
+    scheme, k, skip = int(scheme), int(k), int(skip)
+    what = 'lsq_act_quant_half'
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f'{what}: x must be a bfloat16 or float16 tensor, got {x.dtype}')
+    fp32 = {'scales': scales} if forced is None else {'scales': scales, 'forced': forced}
+    named = ((torch.float32, fp32), (torch.int64, {'planes': planes}), (torch.int32, {} if status is None else {'status': status}))
+    for dtype, group in named:
+        wrong = [name for name, t in group.items() if t.dtype != dtype]
+        if wrong:
+            raise TypeError(f'{what}: {", ".join(wrong)} must be {dtype} tensors')
+    tensors = [x, planes, *fp32.values()] + ([] if status is None else [status])
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: operands must be contiguous')
+    if x.dim() != 4 or x.numel() == 0 or k < 1 or skip < 1:
+        raise ValueError(f'{what}: bad sizes k={k}, skip={skip} for x of shape {tuple(x.shape)}')
+    N, C, H, W = x.shape
+    if (geom.N, geom.C, geom.H, geom.W) != (N, C, H, W) or geom.groups < 1 or C % geom.groups or min(geom.pad_h, geom.pad_w) < 0:
+        raise ValueError(f'{what}: the geometry and x of shape {tuple(x.shape)} do not match')
+    cg = C // geom.groups
+    words = N * geom.groups * ((cg + 63) // 64) * (H + 2 * geom.pad_h) * (W + 2 * geom.pad_w)
+    if (planes.numel() < k * words or any(tuple(t.shape) != (k, N) for t in fp32.values())
+            or (status is not None and tuple(status.shape) != (N,))):
+        raise ValueError(f'{what}: activation planes / scales / status and (k, geometry) do not match')
+    dev = x.device
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError(f'{what}: every operand on the same cuda device')
+    m = C * H * W
+    passes = 1 if forced is not None and k <= 2 else (2 if scheme in (SCHEME_LS2, SCHEME_LST) and forced is None else k)
+    with _on(x), (_Timed(what, N * (2 * m * passes + k * m // 8), 0, f'C{C}_H{H}') if _timing is not None else _UNTIMED):
+        check(conv_act_half_lib().lsq_act_quant_half(
+            x.data_ptr(), LINEAR_HALF_DTYPES[x.dtype], ctypes.byref(geom), scheme, k, skip, float(alpha), ptr(forced),
+            planes.data_ptr(), scales.data_ptr(), ptr(status), stream_ptr(dev)), what)
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

@@ -15,7 +15,14 @@ Dispatch of ``forward``:
   * CUDA tensor in ``train()`` mode, plain geometry -> the same kernels for the forward and the kernels of
     ``quant.binary.hip_train`` for the backward (straight-through estimator, transposed sign-weight convolution), one
     ``torch.autograd.Function`` per call;
-  * anything else (CPU tensors, grouped / dilated training convolutions) -> the torch formulation in ``quant.binary``.
+  * with ``act_half`` set (class attribute, False by default): a bf16 / fp16 CUDA tensor in ``eval()`` mode, binary
+    activations, fp32 weights, autocast off or set to the input's own type -> lsq_act_quant_half
+    (liblsq_hip_conv_act_half.so) reads the 16-bit samples as they are (the clamp bound rounded into their type), then the
+    XNOR convolution as above; the output is its fp32 result rounded once into the input's type.  With
+    ``act_half_kernel = False`` the samples go through ``x.float()`` -> lsq_act_quant instead: the same bits;
+    ``act_half_solve = False`` keeps free-running ``ls-2`` / ``ls-T`` on torch (DESIGN 4.18).  No fallback on this branch;
+  * anything else (CPU tensors, grouped / dilated training convolutions, 16-bit inputs without ``act_half``, with ``fp``
+    activations, 16-bit weights or under an autocast of another type) -> the torch formulation in ``quant.binary``.
 
 Construction, the quantizer / clamp factories, cache invalidation, workspace retention and the eval-side activation
 quantization are ``quant.binary.hip_module.HipQuantModule``'s, shared with ``QuantLinear``; this file keeps what is the
@@ -45,6 +52,18 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: train-mode CUDA tensors through the kernels (False: the torch formulation, e.g. to compare the two in tests)
     hip_train = True
 
+    #: a bf16 / fp16 input (fp32 weights, binary activations, eval mode, autocast off or set to the input's type) takes the
+    #: kernels: lsq_act_quant_half reads the 16-bit samples, lsq_xnor_conv2d computes in fp32 and the result is rounded once
+    #: into the input's type.  False: the torch formulation, the default until the kernel is measured
+    act_half = False
+
+    #: with act_half: the 16-bit input is quantized by lsq_act_quant_half (True) or, for the comparison of DESIGN 4.18, by
+    #: lsq_act_quant on x.float() with the bound rounded into the type (False): the same planes and output bits
+    act_half_kernel = True
+
+    #: with act_half: free-running ls-2 / ls-T activations on a 16-bit input take the kernels too (False: the torch formulation)
+    act_half_solve = True
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
             return self._forward_hip(x)
@@ -68,14 +87,22 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             return False
         if self.w_quant == 'fp':          # nothing binary on the weight side: plain conv
             return False
+        if x.dtype != torch.float32:
+            if torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') != x.dtype:
+                return False              # (a 16-bit input under an autocast of another type: torch decides the types)
+            if (self.x_quant in ('ls-2', 'ls-T') and not self.act_half_solve
+                    and self.x_approximate.eval_scales(x.shape[0]) is None):
+                return False
         return self._hip_supports(x)
 
     def _hip_supports(self, x: torch.Tensor) -> bool:
         """The limits of the kernels (include/lsq_hip.h); anything outside them takes the torch formulation,
-        exactly as training and CPU tensors do: fp32 only, at most 8 bit planes, kernels up to 8x8 on the
+        exactly as training and CPU tensors do: fp32 (bf16 / fp16 inputs with ``act_half``), at most 8 bit planes, kernels up to 8x8 on the
         XNOR path, at most 2^22 sub-sampled keys per row for the LS-2 / LS-T solve."""
         # (memoised per input dtype and row shape: the rest is fixed at construction; _apply -- .to(), .half() -- clears the cache)
         key = ('sup', x.dtype, x.shape[1], x.shape[2], x.shape[3])
+        if x.dtype != torch.float32:
+            key += (self.act_half,)
         hit = self._hip_cache.get(key)
         if hit is None:
             if sum(1 for kk in self._hip_cache if isinstance(kk, tuple) and kk[0] == 'sup') >= 16:      # (many image sizes)
@@ -86,8 +113,11 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
 
     def _hip_supports_uncached(self, x: torch.Tensor) -> bool:
         from quant import _hip
-        if x.dtype != torch.float32 or self.weight.dtype != torch.float32:
+        if self.weight.dtype != torch.float32:
             return False
+        if x.dtype != torch.float32:      # bf16 / fp16: lsq_act_quant_half in front of the fp32 XNOR convolution, on request
+            if x.dtype not in (torch.bfloat16, torch.float16) or not self.act_half or self.x_quant == 'fp':
+                return False
         if getattr(self.w_approximate, 'k', 1) > _hip.MAX_PLANES:      # gf-k weights: k planes
             return False
         if self.x_quant != 'fp':
@@ -124,7 +154,8 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         On the HIP path the eval-mode batch norm is folded into the quantizer's read and the non-linearity /
         shortcut additions into the convolution's epilogue, so none of them is a separate pass over HBM;
         elsewhere it is the plain composition of the modules."""
-        if self._wants_hip(x) and (pre_bn is None or (not pre_bn.training and pre_bn.track_running_stats)):
+        if (x.dtype == torch.float32 and self._wants_hip(x)
+                and (pre_bn is None or (not pre_bn.training and pre_bn.track_running_stats))):
             # next_q = (batch norm or None, QuantConv2d) that will consume the result: with 1-bit activations on both
             # sides the consumer's quantizer runs in THIS convolution's epilogue (quant.binary.chain)
             # res_ready: the residual operands were produced on another stream (the projection shortcut, models/resnet.py);
@@ -214,6 +245,17 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         def join():                      # residual operands from a side stream: in front of the convolution, behind the quantizer
             if res_ready is not None:
                 torch.cuda.current_stream(x.device).wait_event(res_ready)
+        if x.dtype != torch.float32:
+            # a 16-bit input (act_half): the samples are read as they are (or cast: the comparator), the clamp bound as
+            # Tensor.clamp would round it into their type; the fp32 result is rounded once.  No folded batch norm, no fused
+            # epilogue (fused_forward composes them in torch), no chaining.
+            x16 = x.contiguous()
+            k = self.x_approximate.n_planes
+            planes, scales = self._act_planes(x16 if self.act_half_kernel else x16.float(), geom, k, _hip,
+                                              (geom.pad_h, geom.pad_w, self.groups, x.dtype), alpha=self._alpha_in(x.dtype))
+            _hip.xnor_conv2d(planes, k, scales, wbits, wsum, wscales, bias, geom, y)
+            self.last_act_scales = scales
+            return y.to(x.dtype)
         if self.x_quant == 'fp':
             join()
             _hip.signw_conv2d(x, self._alpha(), wbits, wscales, bias, geom, y, pre, relu, res_pre, res_post, prelu, wprep)
