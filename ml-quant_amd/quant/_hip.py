@@ -1193,6 +1193,102 @@ def act_quant_half(x: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: i
             planes.data_ptr(), scales.data_ptr(), ptr(status), stream_ptr(dev)), what)
 
 
+# ---- the 16-bit-activation x sign-weight convolution (include/lsq_hip_conv_half.h): an eleventh shared object, loaded on
+# first use
+_CONV_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_conv_half.so')
+CONV_HALF_ABI_VERSION = 1
+_conv_half_lib = None
+
+
+def conv_half_library_path() -> str:
+    return _CONV_HALF_LIB_PATH
+
+
+def _declare_conv_half(handle):
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    handle.lsq_conv_half_abi_version.restype = i32
+    handle.lsq_conv_half_abi_version.argtypes = []
+    handle.lsq_signw_conv2d_half_plan.restype = i32
+    handle.lsq_signw_conv2d_half_plan.argtypes = [vp]
+    handle.lsq_signw_conv2d_half_workspace_bytes.restype = i64
+    handle.lsq_signw_conv2d_half_workspace_bytes.argtypes = [vp, i32, i32]
+    handle.lsq_signw_conv2d_half.restype = i32
+    handle.lsq_signw_conv2d_half.argtypes = [vp, i32, f32, vp, i32, vp, vp, vp, vp, i32, vp, ctypes.c_size_t, vp]
+
+
+def conv_half_lib():
+    """Load (once) and return the 16-bit-activation convolution library; raises if it has not been built (no fallback, as
+    ``lib()``)."""
+    global _conv_half_lib
+    if _conv_half_lib is None:
+        _conv_half_lib = _load(_CONV_HALF_LIB_PATH, 'csrc/conv_half', _declare_conv_half, 'lsq_conv_half_abi_version',
+                               CONV_HALF_ABI_VERSION, 'liblsq_hip_conv_half.so')
+    return _conv_half_lib
+
+
+def signw_conv2d_half_supported(geom: ConvGeom) -> bool:
+    """Whether lsq_signw_conv2d_half computes ``geom`` (lsq_signw_conv2d_half_plan, host code: no device call): False for a
+    geometry past the library's 32-bit index limits or with an empty output."""
+    return conv_half_lib().lsq_signw_conv2d_half_plan(ctypes.byref(geom)) >= 0
+
+
+_conv_half_ws_cache = {}
+
+
+def signw_conv2d_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: torch.Tensor, bias: Optional[torch.Tensor],
+                      geom: ConvGeom, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """y [N, O, Ho, Wo] = F.conv2d(x.clamp(-alpha, alpha), w_q, bias, ...) for the bf16 / fp16 batch ``x`` [N, C, H, W] of
+    ``geom`` (contiguous, any 2-byte-aligned data pointer) and the sign planes ``wbits`` / fp32 scales ``wscales`` [kw, O]
+    lsq_pack_weight took and wrote for ``geom`` (lsq_signw_conv2d_half); ``alpha`` is the symmetric clamp bound ALREADY
+    ROUNDED into x's type (as Tensor.clamp rounds it), negative for none.  ``out_dtype``: x.dtype (the default) or
+    torch.float32; the 16-bit result is the fp32 one rounded once.  The fp32 running sum of a 16-bit result of more than one
+    plane lives in a workspace cached per (device, stream) like the solver's (rewritten by every call; kernels of one stream
+    run in order)."""
+    what = 'lsq_signw_conv2d_half'
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f'{what}: x must be a bfloat16 or float16 tensor, got {x.dtype}')
+    if out_dtype not in (torch.float32, x.dtype):
+        raise TypeError(f'{what}: out_dtype must be torch.float32 or {x.dtype}, got {out_dtype}')
+    fp32 = {'wscales': wscales} if bias is None else {'wscales': wscales, 'bias': bias}
+    wrong = [name for name, t in fp32.items() if t.dtype != torch.float32]
+    if wrong:
+        raise TypeError(f'{what}: {", ".join(wrong)} must be torch.float32 tensors')
+    if wbits.dtype != torch.int64:
+        raise TypeError(f'{what}: wbits must be a torch.int64 tensor')
+    tensors = [x, wbits, *fp32.values()]
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: operands must be contiguous')
+    if x.dim() != 4 or x.numel() == 0 or wscales.dim() != 2 or wscales.shape[0] < 1:
+        raise ValueError(f'{what}: bad sizes: x of shape {tuple(x.shape)}, wscales of shape {tuple(wscales.shape)}')
+    N, C, H, W = x.shape
+    if ((geom.N, geom.C, geom.H, geom.W) != (N, C, H, W) or min(geom.O, geom.KH, geom.KW, geom.groups) < 1
+            or C % geom.groups or geom.O % geom.groups):
+        raise ValueError(f'{what}: the geometry and x of shape {tuple(x.shape)} do not match')
+    kw, O = wscales.shape[0], geom.O
+    words = geom.KH * geom.KW * ((C // geom.groups + 63) // 64) * geom.groups * ((O // geom.groups + 15) // 16 * 16)
+    if wscales.shape[1] != O or wbits.numel() < kw * words or (bias is not None and tuple(bias.shape) != (O,)):
+        raise ValueError(f'{what}: weight planes / scales / bias and (kw, geometry) do not match')
+    dev = x.device
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError(f'{what}: every operand on the same cuda device')
+    ho, wo = out_hw(geom)
+    if ho < 1 or wo < 1:
+        raise ValueError(f'{what}: the geometry has an empty output')
+    hl = conv_half_lib()
+    xdt, ydt = LINEAR_HALF_DTYPES[x.dtype], LINEAR_HALF_DTYPES[out_dtype]
+    need = int(hl.lsq_signw_conv2d_half_workspace_bytes(ctypes.byref(geom), kw, ydt))
+    ws = _stream_buffer(_conv_half_ws_cache, need, dev) if need else None
+    y = torch.empty((N, O, ho, wo), dtype=out_dtype, device=dev)
+    nbytes = 2 * x.numel() + 8 * y.numel() * (kw - 1) + y.element_size() * y.numel()    # (the fp32 sum is read back per plane)
+    with _on(y), (_Timed(what, nbytes, 2 * y.numel() * (C // geom.groups) * geom.KH * geom.KW * kw,
+                         f'C{C}_H{H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
+        check(hl.lsq_signw_conv2d_half(x.data_ptr(), xdt, float(alpha), wbits.data_ptr(), kw, wscales.data_ptr(), ptr(bias),
+                                       ctypes.byref(geom), y.data_ptr(), ydt, ptr(ws), 0 if ws is None else ws.numel(),
+                                       stream_ptr(dev)), what)
+    return y
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

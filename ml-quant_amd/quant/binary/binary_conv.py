@@ -21,8 +21,15 @@ Dispatch of ``forward``:
     XNOR convolution as above; the output is its fp32 result rounded once into the input's type.  With
     ``act_half_kernel = False`` the samples go through ``x.float()`` -> lsq_act_quant instead: the same bits;
     ``act_half_solve = False`` keeps free-running ``ls-2`` / ``ls-T`` on torch (DESIGN 4.18).  No fallback on this branch;
-  * anything else (CPU tensors, grouped / dilated training convolutions, 16-bit inputs without ``act_half``, with ``fp``
-    activations, 16-bit weights or under an autocast of another type) -> the torch formulation in ``quant.binary``.
+  * with ``fp_half`` set (class attribute, False by default, a switch of its own beside ``act_half``): a bf16 / fp16 CUDA
+    tensor in ``eval()`` mode, ``fp`` activations, binary fp32 weights, autocast off or set to the input's own type ->
+    lsq_signw_conv2d_half (liblsq_hip_conv_half.so) reads the 16-bit samples as they are (the clamp bound rounded into their
+    type) against the weight sign planes, with fp32 weight scales and fp32 accumulation; the output is its fp32 result
+    rounded once into the input's type.  With ``fp_half_kernel = False`` the samples go through ``x.float()`` ->
+    lsq_signw_conv2d instead, the comparator of DESIGN 4.19.  No fallback on this branch;
+  * anything else (CPU tensors, grouped / dilated training convolutions, 16-bit inputs with binary activations without
+    ``act_half`` or with ``fp`` activations without ``fp_half``, 16-bit weights, an autocast of another type) -> the torch
+    formulation in ``quant.binary``.
 
 Construction, the quantizer / clamp factories, cache invalidation, workspace retention and the eval-side activation
 quantization are ``quant.binary.hip_module.HipQuantModule``'s, shared with ``QuantLinear``; this file keeps what is the
@@ -64,6 +71,15 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: with act_half: free-running ls-2 / ls-T activations on a 16-bit input take the kernels too (False: the torch formulation)
     act_half_solve = True
 
+    #: a bf16 / fp16 input with ``fp`` activations (binary fp32 weights, eval mode, autocast off or set to the input's type)
+    #: takes lsq_signw_conv2d_half: the 16-bit samples against the sign planes, fp32 scales and accumulation, rounded once into
+    #: the input's type.  False: the torch formulation, the default until the kernel is measured
+    fp_half = False
+
+    #: with fp_half: the 16-bit input is convolved by lsq_signw_conv2d_half (True) or, for the comparison of DESIGN 4.19, by
+    #: lsq_signw_conv2d on x.float() with the bound rounded into the type (False)
+    fp_half_kernel = True
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
             return self._forward_hip(x)
@@ -97,12 +113,14 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
 
     def _hip_supports(self, x: torch.Tensor) -> bool:
         """The limits of the kernels (include/lsq_hip.h); anything outside them takes the torch formulation,
-        exactly as training and CPU tensors do: fp32 (bf16 / fp16 inputs with ``act_half``), at most 8 bit planes, kernels up to 8x8 on the
+        exactly as training and CPU tensors do: fp32 (bf16 / fp16 inputs with ``act_half`` / ``fp_half``), at most 8 bit planes, kernels up to 8x8 on the
         XNOR path, at most 2^22 sub-sampled keys per row for the LS-2 / LS-T solve."""
         # (memoised per input dtype and row shape: the rest is fixed at construction; _apply -- .to(), .half() -- clears the cache)
         key = ('sup', x.dtype, x.shape[1], x.shape[2], x.shape[3])
         if x.dtype != torch.float32:
-            key += (self.act_half,)
+            key += (self.act_half, self.fp_half)
+            if self.x_quant == 'fp':      # (lsq_signw_conv2d_half's index limits depend on the batch size too)
+                key += (x.shape[0],)
         hit = self._hip_cache.get(key)
         if hit is None:
             if sum(1 for kk in self._hip_cache if isinstance(kk, tuple) and kk[0] == 'sup') >= 16:      # (many image sizes)
@@ -115,9 +133,13 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         from quant import _hip
         if self.weight.dtype != torch.float32:
             return False
-        if x.dtype != torch.float32:      # bf16 / fp16: lsq_act_quant_half in front of the fp32 XNOR convolution, on request
-            if x.dtype not in (torch.bfloat16, torch.float16) or not self.act_half or self.x_quant == 'fp':
+        if x.dtype != torch.float32:      # bf16 / fp16, on request: lsq_act_quant_half in front of the fp32 XNOR convolution,
+            if x.dtype not in (torch.bfloat16, torch.float16):          # or lsq_signw_conv2d_half for fp activations
                 return False
+            if not (self.fp_half if self.x_quant == 'fp' else self.act_half):
+                return False
+            if self.x_quant == 'fp' and not _hip.signw_conv2d_half_supported(self._geom_of(x, _hip)):
+                return False              # (past the library's 32-bit index limits, include/lsq_hip_conv_half.h)
         if getattr(self.w_approximate, 'k', 1) > _hip.MAX_PLANES:      # gf-k weights: k planes
             return False
         if self.x_quant != 'fp':
@@ -130,7 +152,15 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         return True
 
     # ------------------------------------------------------------------ HIP path
-    def _packed_weights(self, geom, _hip):
+    def _geom_of(self, x: torch.Tensor, _hip):
+        n, c, h, w = x.shape
+        kh, kw = self.kernel_size
+        return _hip.make_geom(n, c, h, w, self.out_channels, kh, kw, self.stride, self.padding, self.dilation, self.groups)
+
+    def _packed_weights(self, geom, _hip, prep: bool = True):
+        """(wbits, wsum, wscales, wprep) of this eval session.  ``prep``: the caller reads ``wprep``, the bf16 operand image of
+        lsq_signw_conv2d's 3x3 fast path (fp activations only); it is built with the planes, or by the first call that asks
+        for it -- lsq_signw_conv2d_half never does."""
         wq = self.w_approximate
         bufs = wq.cached_scales()
         w = self._parameters['weight']
@@ -139,10 +169,12 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         if hit is None or hit[0] != stamp:
             scales = wq.plane_scales().to(torch.float32).contiguous()
             wbits, wsum = _hip.pack_weight(self.weight.detach(), geom, scales)
-            # fp activations: the bf16 operand image of the 3x3 fast path, built once with the planes
-            wprep = _hip.signw_prepare_weight(wbits, scales.shape[0], geom) if self.x_quant == 'fp' else None
-            hit = (stamp, wbits, wsum, scales, wprep)
+            hit = [stamp, wbits, wsum, scales, None, False]          # (wprep, and whether it has been asked for)
             self._hip_cache['w'] = hit
+        if prep and not hit[5]:
+            # fp activations: the bf16 operand image of the 3x3 fast path, built once per session
+            hit[4] = _hip.signw_prepare_weight(hit[1], hit[3].shape[0], geom) if self.x_quant == 'fp' else None
+            hit[5] = True
         return hit[1], hit[2], hit[3], hit[4]
 
     def fused_forward(self, x: torch.Tensor, pre_bn: Optional[nn.BatchNorm2d] = None, relu: bool = False,
@@ -232,24 +264,30 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         handed = chain.pending(x)                  # (an attribute of the tensor object: read before detach())
         x = x.detach()
         pre = None if pre_bn is None else self._folded_bn(pre_bn)
-        n, c, h, w = x.shape
-        kh, kw = self.kernel_size
-        geom = _hip.make_geom(n, c, h, w, self.out_channels, kh, kw, self.stride, self.padding,
-                              self.dilation, self.groups)
-        wbits, wsum, wscales, wprep = self._packed_weights(geom, _hip)
+        n = x.shape[0]
+        geom = self._geom_of(x, _hip)
+        half_kernel = x.dtype != torch.float32 and self.x_quant == 'fp' and self.fp_half_kernel
+        wbits, wsum, wscales, wprep = self._packed_weights(geom, _hip, prep=not half_kernel)
         ho, wo = _hip.out_hw(geom)
         res_pre = None if res_pre is None else res_pre.detach().contiguous()
         res_post = None if res_post is None else res_post.detach().contiguous()
-        y = torch.empty((n, self.out_channels, ho, wo), dtype=torch.float32, device=x.device)
         bias = None if self.bias is None else self.bias.detach()
+        if half_kernel:
+            # a 16-bit input with fp activations (fp_half): the samples as they are against the sign planes, the clamp bound as
+            # Tensor.clamp would round it into their type; the kernel rounds its fp32 result once into the input's type
+            return _hip.signw_conv2d_half(x.contiguous(), self._alpha_in(x.dtype), wbits, wscales, bias, geom)
+        y = torch.empty((n, self.out_channels, ho, wo), dtype=torch.float32, device=x.device)
         def join():                      # residual operands from a side stream: in front of the convolution, behind the quantizer
             if res_ready is not None:
                 torch.cuda.current_stream(x.device).wait_event(res_ready)
         if x.dtype != torch.float32:
-            # a 16-bit input (act_half): the samples are read as they are (or cast: the comparator), the clamp bound as
-            # Tensor.clamp would round it into their type; the fp32 result is rounded once.  No folded batch norm, no fused
+            # a 16-bit input (act_half / fp_half): the samples are read as they are (or cast: the comparator), the clamp bound
+            # as Tensor.clamp would round it into their type; the fp32 result is rounded once.  No folded batch norm, no fused
             # epilogue (fused_forward composes them in torch), no chaining.
             x16 = x.contiguous()
+            if self.x_quant == 'fp':          # (fp_half_kernel = False: the cast route, the comparator of DESIGN 4.19)
+                _hip.signw_conv2d(x16.float(), self._alpha_in(x.dtype), wbits, wscales, bias, geom, y, wprep=wprep)
+                return y.to(x.dtype)
             k = self.x_approximate.n_planes
             planes, scales = self._act_planes(x16 if self.act_half_kernel else x16.float(), geom, k, _hip,
                                               (geom.pad_h, geom.pad_w, self.groups, x.dtype), alpha=self._alpha_in(x.dtype))
