@@ -1289,6 +1289,97 @@ def signw_conv2d_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscale
     return y
 
 
+# ---- the convolution layer's training library (include/lsq_hip_conv_train.h): a twelfth shared object, loaded on first use
+_CONV_TRAIN_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_conv_train.so')
+CONV_TRAIN_ABI_VERSION = 1
+_conv_train_lib = None
+
+
+class ConvDgradPlan(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'classes', 'dead_classes', 'tap_steps')]
+
+
+def conv_train_library_path() -> str:
+    return _CONV_TRAIN_LIB_PATH
+
+
+def _declare_conv_train(handle):
+    vp, i32 = ctypes.c_void_p, ctypes.c_int
+    handle.lsq_conv_train_abi_version.restype = i32
+    handle.lsq_conv_train_abi_version.argtypes = []
+    handle.lsq_signw_conv2d_dgrad_plan.restype = i32
+    handle.lsq_signw_conv2d_dgrad_plan.argtypes = [vp, vp]
+    handle.lsq_signw_conv2d_dgrad_workspace_bytes.restype = ctypes.c_size_t
+    handle.lsq_signw_conv2d_dgrad_workspace_bytes.argtypes = [vp, i32]
+    handle.lsq_signw_conv2d_dgrad.restype = i32
+    handle.lsq_signw_conv2d_dgrad.argtypes = [vp, vp, i32, vp, vp, vp, vp, ctypes.c_size_t, vp]
+
+
+def conv_train_lib():
+    """Load (once) and return the convolution layer's training library; raises if it has not been built (no fallback, as
+    ``lib()``)."""
+    global _conv_train_lib
+    if _conv_train_lib is None:
+        _conv_train_lib = _load(_CONV_TRAIN_LIB_PATH, 'csrc/conv_train', _declare_conv_train, 'lsq_conv_train_abi_version',
+                                CONV_TRAIN_ABI_VERSION, 'liblsq_hip_conv_train.so')
+    return _conv_train_lib
+
+
+def signw_conv2d_dgrad_plan(geom: ConvGeom) -> Optional[ConvDgradPlan]:
+    """The plan of lsq_signw_conv2d_dgrad for the forward geometry ``geom`` (host code: no device call), None where the
+    call would refuse it."""
+    plan = ConvDgradPlan()
+    return plan if conv_train_lib().lsq_signw_conv2d_dgrad_plan(ctypes.byref(geom), ctypes.byref(plan)) == 0 else None
+
+
+def signw_conv2d_dgrad_supported(geom: ConvGeom) -> bool:
+    """Whether lsq_signw_conv2d_dgrad computes the forward geometry ``geom``: False past the library's 32-bit index and grid
+    limits or with an empty output."""
+    return signw_conv2d_dgrad_plan(geom) is not None
+
+
+_conv_dgrad_ws_cache = {}
+
+
+def signw_conv2d_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Tensor, geom: ConvGeom) -> torch.Tensor:
+    """grad_xq [N, C, H, W] = conv2d_input(w_q, gy) for the fp32 output gradient ``gy`` [N, O, Ho, Wo] of the FORWARD geometry
+    ``geom`` and the sign planes ``wbits`` / scales ``wscales`` [kw, O] lsq_pack_weight took and wrote for ``geom`` -- the
+    forward's own operands (lsq_signw_conv2d_dgrad).  The transposed plane image lives in a workspace cached per
+    (device, stream) like the solver's (rewritten by every call; kernels of one stream run in order)."""
+    what = 'lsq_signw_conv2d_dgrad'
+    wrong = [name for name, t in (('gy', gy), ('wscales', wscales)) if t.dtype != torch.float32]
+    if wrong:
+        raise TypeError(f'{what}: {", ".join(wrong)} must be torch.float32 tensors')
+    if wbits.dtype != torch.int64:
+        raise TypeError(f'{what}: wbits must be a torch.int64 tensor')
+    tensors = [gy, wbits, wscales]
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: operands must be contiguous')
+    if gy.dim() != 4 or gy.numel() == 0 or wscales.dim() != 2 or not 1 <= wscales.shape[0] <= MAX_PLANES:
+        raise ValueError(f'{what}: bad sizes: gy of shape {tuple(gy.shape)}, wscales of shape {tuple(wscales.shape)}')
+    if (min(geom.N, geom.C, geom.H, geom.W, geom.O, geom.KH, geom.KW, geom.groups, geom.stride_h, geom.stride_w,
+            geom.dil_h, geom.dil_w) < 1 or min(geom.pad_h, geom.pad_w) < 0 or geom.C % geom.groups or geom.O % geom.groups
+            or tuple(gy.shape) != (geom.N, geom.O) + tuple(out_hw(geom))):
+        raise ValueError(f'{what}: the geometry and gy of shape {tuple(gy.shape)} do not match')
+    kw, O, C = wscales.shape[0], geom.O, geom.C
+    words = geom.KH * geom.KW * ((C // geom.groups + 63) // 64) * geom.groups * ((O // geom.groups + 15) // 16 * 16)
+    if wscales.shape[1] != O or wbits.numel() != kw * words:
+        raise ValueError(f'{what}: weight planes / scales and (kw, geometry) do not match')
+    dev = gy.device
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError(f'{what}: every operand on the same cuda device')
+    tl = conv_train_lib()
+    need = int(tl.lsq_signw_conv2d_dgrad_workspace_bytes(ctypes.byref(geom), kw))
+    ws = _stream_buffer(_conv_dgrad_ws_cache, need, dev) if need else None
+    gx = torch.empty((geom.N, C, geom.H, geom.W), dtype=torch.float32, device=dev)
+    with _on(gx), (_Timed(what, 4 * gy.numel() + 8 * kw * words + 2 * need + 4 * gx.numel(),
+                          2 * 2 * gy.numel() * (C // geom.groups) * geom.KH * geom.KW * kw,       # (hi and lo pass)
+                          f'C{C}_H{geom.H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
+        check(tl.lsq_signw_conv2d_dgrad(gy.data_ptr(), wbits.data_ptr(), kw, wscales.data_ptr(), ctypes.byref(geom),
+                                        gx.data_ptr(), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev)), what)
+    return gx
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

@@ -25,6 +25,10 @@ backward  grad_bias = sum of grad_y;
           grad_w    = ``lsq_ste_backward`` over the weight rows.
 Geometries the transposed convolution does not take (groups, dilation, strides other than 1 / 2) fall back to the torch
 formulation of the module; results are those of the reference's graph within fp32 reassociation (tests: f9_train).
+With ``DGRAD_KERNEL`` (False by default) grad_xq is ONE ``lsq_signw_conv2d_dgrad`` (liblsq_hip_conv_train.so) over
+the forward's own weight planes, saved with the step: no residual planes, no permute / flip, no second packing and no
+zero-inserted gradient; every geometry that kernel's plan accepts (groups, dilation, any stride pair, any padding) then
+takes the kernels, and the weight gradient takes ``lsq_train_wgrad`` only where that kernel's stated geometry holds.
 The forward's weight side and activation side (forced scales, moving averages) and the module's plane workspace are
 ``quant.binary.hip_train_common``'s, shared with ``hip_train_linear``; its retention policy is ``HipQuantModule._workspace``.
 """
@@ -42,6 +46,19 @@ from quant.binary.hip_train_common import step_act_quant, step_planes, step_weig
 # profiles/train_step.json) -- the kernel stays the default only once it makes the step faster.
 WGRAD_KERNEL = False
 
+# the input gradient on lsq_signw_conv2d_dgrad (True) or on lsq_signw_conv2d in the transposed role, one launch per weight
+# plane over re-packed planes, stride 2 by zero insertion (False).  Off by default: the landing rule of WGRAD_KERNEL (DESIGN
+# 4.20 holds what was measured).
+DGRAD_KERNEL = False
+
+
+def _wgrad_geometry(conv) -> bool:
+    """The geometry lsq_train_wgrad states (include/lsq_hip_train.h): groups 1, dilation 1, one stride of 1 or 2, padding
+    <= kernel - 1, kernels up to 8 x 8."""
+    kh, kw = conv.kernel_size
+    return (conv.groups == 1 and tuple(conv.dilation) == (1, 1) and conv.stride[0] == conv.stride[1] and conv.stride[0] in (1, 2)
+            and conv.padding[0] <= kh - 1 and conv.padding[1] <= kw - 1 and max(kh, kw) <= 8)
+
 
 def supported(conv, x: torch.Tensor) -> bool:
     """Train-mode forward + backward on the kernels: fp32 4-d CUDA input, binary weights, plain geometry -- and the library
@@ -53,11 +70,16 @@ def supported(conv, x: torch.Tensor) -> bool:
         return False
     if conv.w_quant == 'fp' or conv.padding_mode != 'zeros' or isinstance(conv.padding, str):
         return False
-    if conv.groups != 1 or tuple(conv.dilation) != (1, 1) or conv.stride[0] != conv.stride[1] or conv.stride[0] not in (1, 2):
-        return False
-    kh, kw = conv.kernel_size
-    if conv.padding[0] > kh - 1 or conv.padding[1] > kw - 1:
-        return False
+    if DGRAD_KERNEL:
+        # what the plan of lsq_signw_conv2d_dgrad accepts (a missing library raises: the switch asked for the kernel)
+        if not _hip.signw_conv2d_dgrad_supported(conv._geom_of(x, _hip)):
+            return False
+    else:
+        if conv.groups != 1 or tuple(conv.dilation) != (1, 1) or conv.stride[0] != conv.stride[1] or conv.stride[0] not in (1, 2):
+            return False
+        kh, kw = conv.kernel_size
+        if conv.padding[0] > kh - 1 or conv.padding[1] > kw - 1:
+            return False
     if x.shape[0] > 65535 or conv.out_channels > 65535:
         return False
     return conv._hip_supports(x)
@@ -95,17 +117,19 @@ class _QuantConv2dStep(torch.autograd.Function):
         n, c, h, w = x.shape
         kh, kw = conv.kernel_size
         alpha = conv._alpha()
-        geom = _hip.make_geom(n, c, h, w, conv.out_channels, kh, kw, conv.stride, conv.padding, conv.dilation, 1)
+        geom = _hip.make_geom(n, c, h, w, conv.out_channels, kh, kw, conv.stride, conv.padding, conv.dilation, conv.groups)
         ho, wo = _hip.out_hw(geom)
         wscales, wbits, wsum = step_weight_planes(conv, weight.detach(), geom, _hip)
         y = torch.empty((n, conv.out_channels, ho, wo), dtype=torch.float32, device=x.device)
         b = None if bias is None else bias.detach()
+        keep_planes = False
         if conv.x_quant == 'fp':
             _hip.signw_conv2d(x.detach(), alpha, wbits, wscales, b, geom, y)
             xscales = None
         else:
             k = conv.x_approximate.n_planes
-            if WGRAD_KERNEL and ctx.needs_input_grad[1]:
+            keep_planes = WGRAD_KERNEL and ctx.needs_input_grad[1] and _wgrad_geometry(conv)
+            if keep_planes:
                 # backward reads these planes: a buffer of this step (zero halo), saved with it
                 planes = zero_planes(geom, k, x.device, _hip)
             else:
@@ -115,9 +139,12 @@ class _QuantConv2dStep(torch.autograd.Function):
             conv.last_act_scales = xscales
         ctx.conv, ctx.geom, ctx.alpha = conv, geom, alpha
         ctx.has_bias = bias is not None
-        saved_planes = planes if (xscales is not None and WGRAD_KERNEL and ctx.needs_input_grad[1]) else None
+        saved_planes = planes if (xscales is not None and keep_planes) else None
+        # lsq_signw_conv2d_dgrad reads this step's weight planes (a tensor of the step: a second forward packs its own)
+        saved_wbits = wbits if (DGRAD_KERNEL and ctx.needs_input_grad[0]) else None
         ctx.save_for_backward(x, weight, wscales, xscales if xscales is not None else x.new_empty(0),
-                              saved_planes if saved_planes is not None else x.new_empty(0, dtype=torch.int64))
+                              saved_planes if saved_planes is not None else x.new_empty(0, dtype=torch.int64),
+                              saved_wbits if saved_wbits is not None else x.new_empty(0, dtype=torch.int64))
         return y
 
     @staticmethod
@@ -125,7 +152,7 @@ class _QuantConv2dStep(torch.autograd.Function):
     def backward(ctx, gy):
         from quant import _hip
         conv, geom, alpha = ctx.conv, ctx.geom, ctx.alpha
-        x, weight, wscales, xscales, planes = ctx.saved_tensors
+        x, weight, wscales, xscales, planes, wbits = ctx.saved_tensors
         xscales = xscales if xscales.numel() else None
         gy = gy.contiguous()
         n, c, h, w = x.shape
@@ -137,7 +164,9 @@ class _QuantConv2dStep(torch.autograd.Function):
         gx = gw = gb = None
         if need_b:
             gb = gy.sum(dim=(0, 2, 3))
-        if need_x:
+        if need_x and wbits.numel():
+            gx = _hip.ste_backward(x, _hip.signw_conv2d_dgrad(gy, wbits, wscales, geom), xscales, alpha)
+        elif need_x:
             # conv_transpose2d(gy, w_q) as stride-1 sign-weight convolutions of the (zero-inserted) gradient
             if s == 1:
                 gin = gy
@@ -161,7 +190,7 @@ class _QuantConv2dStep(torch.autograd.Function):
                 gwq = _hip.wgrad(planes, xscales.shape[0], xscales, gy, geom)
             else:
                 xq = _hip.quant_values(x, xscales, alpha)
-                gwq = torch.nn.grad.conv2d_weight(xq, weight.shape, gy, conv.stride, conv.padding, conv.dilation, 1)
+                gwq = torch.nn.grad.conv2d_weight(xq, weight.shape, gy, conv.stride, conv.padding, conv.dilation, conv.groups)
             gw = _hip.ste_backward(weight.detach(), gwq, wscales, -1.0)
         return gx, gw, gb, None
 
