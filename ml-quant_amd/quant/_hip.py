@@ -1380,6 +1380,124 @@ def signw_conv2d_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Ten
     return gx
 
 
+# ---- the convolution layer's 16-bit training library (include/lsq_hip_conv_train_half.h): a thirteenth shared object, loaded
+# on first use
+_CONV_TRAIN_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_conv_train_half.so')
+CONV_TRAIN_HALF_ABI_VERSION = 1
+CONV_DGRAD_HALF_MAX_SAMPLES = 65535    # lsq_signw_conv2d_dgrad_half with x: N <= 65535 (the limit of lsq_ste_backward)
+_conv_train_half_lib = None
+
+
+def conv_train_half_library_path() -> str:
+    return _CONV_TRAIN_HALF_LIB_PATH
+
+
+def _declare_conv_train_half(handle):
+    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    handle.lsq_conv_train_half_abi_version.restype = i32
+    handle.lsq_conv_train_half_abi_version.argtypes = []
+    handle.lsq_signw_conv2d_dgrad_half_plan.restype = i32
+    handle.lsq_signw_conv2d_dgrad_half_plan.argtypes = [vp, vp]
+    handle.lsq_signw_conv2d_dgrad_half_workspace_bytes.restype = ctypes.c_size_t
+    handle.lsq_signw_conv2d_dgrad_half_workspace_bytes.argtypes = [vp, i32]
+    handle.lsq_signw_conv2d_dgrad_half.restype = i32
+    handle.lsq_signw_conv2d_dgrad_half.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, ctypes.c_size_t, vp]
+
+
+def conv_train_half_lib():
+    """Load (once) and return the convolution layer's 16-bit training library; raises if it has not been built (no fallback,
+    as ``lib()``)."""
+    global _conv_train_half_lib
+    if _conv_train_half_lib is None:
+        _conv_train_half_lib = _load(_CONV_TRAIN_HALF_LIB_PATH, 'csrc/conv_train_half', _declare_conv_train_half,
+                                     'lsq_conv_train_half_abi_version', CONV_TRAIN_HALF_ABI_VERSION,
+                                     'liblsq_hip_conv_train_half.so')
+    return _conv_train_half_lib
+
+
+def signw_conv2d_dgrad_half_plan(geom: ConvGeom) -> Optional[ConvDgradPlan]:
+    """The plan of lsq_signw_conv2d_dgrad_half for the forward geometry ``geom`` (host code: no device call), None where the
+    call would refuse it: for every geometry what ``signw_conv2d_dgrad_plan`` returns."""
+    plan = ConvDgradPlan()
+    return plan if conv_train_half_lib().lsq_signw_conv2d_dgrad_half_plan(ctypes.byref(geom), ctypes.byref(plan)) == 0 else None
+
+
+def signw_conv2d_dgrad_half_supported(geom: ConvGeom) -> bool:
+    """Whether lsq_signw_conv2d_dgrad_half computes the forward geometry ``geom``: False past the library's 32-bit index and
+    grid limits or with an empty output."""
+    return signw_conv2d_dgrad_half_plan(geom) is not None
+
+
+_conv_dgrad_half_ws_cache = {}
+
+
+def signw_conv2d_dgrad_half(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Tensor, geom: ConvGeom,
+                            x: Optional[torch.Tensor] = None, xscales: Optional[torch.Tensor] = None, alpha: float = -1.0,
+                            out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """grad_x [N, C, H, W] of the 16-bit train step in one launch (lsq_signw_conv2d_dgrad_half): conv2d_input(w_q, gy) for the
+    bf16 / fp16 output gradient ``gy`` [N, O, Ho, Wo] of the FORWARD geometry ``geom`` (contiguous, any 2-byte-aligned data
+    pointer) and the forward's own sign planes ``wbits`` / fp32 scales ``wscales`` [kw, O]; with ``x`` (the step's input
+    [N, C, H, W] of gy's type) the result then goes through the straight-through estimator of the activation quantizer --
+    ``xscales`` [kx, N] fp32, None for fp activations -- and the clamp ``alpha``, the bound ALREADY ROUNDED into the type
+    (negative: none).  ``out_dtype``: gy.dtype (the default) or torch.float32; the 16-bit result is the fp32 one rounded
+    once.  With ``x`` the batch is at most 65535 samples (the limit of lsq_ste_backward).  The transposed plane image lives
+    in a workspace cached per (device, stream) like the solver's (rewritten by every call; kernels of one stream run in
+    order)."""
+    what = 'lsq_signw_conv2d_dgrad_half'
+    if gy.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f'{what}: gy must be a bfloat16 or float16 tensor, got {gy.dtype}')
+    out_dtype = gy.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, gy.dtype):
+        raise TypeError(f'{what}: out_dtype must be torch.float32 or {gy.dtype}, got {out_dtype}')
+    if x is not None and x.dtype != gy.dtype:
+        raise TypeError(f'{what}: x must be of gy\'s type {gy.dtype}, got {x.dtype}')
+    fp32 = {'wscales': wscales} if xscales is None else {'wscales': wscales, 'xscales': xscales}
+    wrong = [name for name, t in fp32.items() if t.dtype != torch.float32]
+    if wrong:
+        raise TypeError(f'{what}: {", ".join(wrong)} must be torch.float32 tensors')
+    if wbits.dtype != torch.int64:
+        raise TypeError(f'{what}: wbits must be a torch.int64 tensor')
+    if xscales is not None and x is None:
+        raise ValueError(f'{what}: xscales without x')
+    tensors = [gy, wbits, *fp32.values()] + ([] if x is None else [x])
+    if any(not t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: operands must be contiguous')
+    if gy.dim() != 4 or gy.numel() == 0 or wscales.dim() != 2 or not 1 <= wscales.shape[0] <= MAX_PLANES:
+        raise ValueError(f'{what}: bad sizes: gy of shape {tuple(gy.shape)}, wscales of shape {tuple(wscales.shape)}')
+    if xscales is not None and (xscales.dim() != 2 or not 1 <= xscales.shape[0] <= MAX_PLANES):
+        raise ValueError(f'{what}: bad sizes: xscales of shape {tuple(xscales.shape)}')
+    if (min(geom.N, geom.C, geom.H, geom.W, geom.O, geom.KH, geom.KW, geom.groups, geom.stride_h, geom.stride_w,
+            geom.dil_h, geom.dil_w) < 1 or min(geom.pad_h, geom.pad_w) < 0 or geom.C % geom.groups or geom.O % geom.groups
+            or tuple(gy.shape) != (geom.N, geom.O) + tuple(out_hw(geom))):
+        raise ValueError(f'{what}: the geometry and gy of shape {tuple(gy.shape)} do not match')
+    kw, O, C = wscales.shape[0], geom.O, geom.C
+    words = geom.KH * geom.KW * ((C // geom.groups + 63) // 64) * geom.groups * ((O // geom.groups + 15) // 16 * 16)
+    if wscales.shape[1] != O or wbits.numel() != kw * words:
+        raise ValueError(f'{what}: weight planes / scales and (kw, geometry) do not match')
+    if x is not None and tuple(x.shape) != (geom.N, C, geom.H, geom.W):
+        raise ValueError(f'{what}: the geometry and x of shape {tuple(x.shape)} do not match')
+    if xscales is not None and xscales.shape[1] != geom.N:
+        raise ValueError(f'{what}: activation scales and (kx, geometry) do not match')
+    if x is not None and geom.N > CONV_DGRAD_HALF_MAX_SAMPLES:
+        raise ValueError(f'{what}: at most {CONV_DGRAD_HALF_MAX_SAMPLES} samples with x, got {geom.N}')
+    dev = gy.device
+    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
+        raise ValueError(f'{what}: every operand on the same cuda device')
+    tl = conv_train_half_lib()
+    need = int(tl.lsq_signw_conv2d_dgrad_half_workspace_bytes(ctypes.byref(geom), kw))
+    ws = _stream_buffer(_conv_dgrad_half_ws_cache, need, dev) if need else None
+    gx = torch.empty((geom.N, C, geom.H, geom.W), dtype=out_dtype, device=dev)
+    kx = 0 if xscales is None else xscales.shape[0]
+    nbytes = 2 * gy.numel() + 8 * kw * words + 2 * need + gx.element_size() * gx.numel() + (0 if x is None else 2 * x.numel())
+    with _on(gx), (_Timed(what, nbytes, 2 * 2 * gy.numel() * (C // geom.groups) * geom.KH * geom.KW * kw,       # (hi and lo pass)
+                          f'C{C}_H{geom.H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
+        check(tl.lsq_signw_conv2d_dgrad_half(gy.data_ptr(), LINEAR_HALF_DTYPES[gy.dtype], wbits.data_ptr(), kw,
+                                             wscales.data_ptr(), ctypes.byref(geom), ptr(x), kx, ptr(xscales), float(alpha),
+                                             gx.data_ptr(), LINEAR_HALF_DTYPES[out_dtype], ptr(ws),
+                                             0 if ws is None else ws.numel(), stream_ptr(dev)), what)
+    return gx
+
+
 def xnor_impl(mode) -> int:
     """Test / profiling hook (include/lsq_hip_debug.h): 1 / True = every XNOR convolution through the popcount kernel, 0 / False
     = the dispatcher picks the matrix-core kernel where it applies (fp4 operands on the scaled MFMA, the default), 2 = the

@@ -27,6 +27,9 @@ Dispatch of ``forward``:
     type) against the weight sign planes, with fp32 weight scales and fp32 accumulation; the output is its fp32 result
     rounded once into the input's type.  With ``fp_half_kernel = False`` the samples go through ``x.float()`` ->
     lsq_signw_conv2d instead, the comparator of DESIGN 4.19.  No fallback on this branch;
+  * with ``hip_train_half`` set (class attribute, False by default): a bf16 / fp16 CUDA tensor in ``train()`` mode, binary fp32
+    weights, autocast off or set to the input's own type -> the 16-bit step of ``quant.binary.hip_train``:
+    lsq_act_quant_half / lsq_signw_conv2d_half forward, one lsq_signw_conv2d_dgrad_half for the input gradient;
   * anything else (CPU tensors, grouped / dilated training convolutions, 16-bit inputs with binary activations without
     ``act_half`` or with ``fp`` activations without ``fp_half``, 16-bit weights, an autocast of another type) -> the torch
     formulation in ``quant.binary``.
@@ -79,6 +82,12 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: with fp_half: the 16-bit input is convolved by lsq_signw_conv2d_half (True) or, for the comparison of DESIGN 4.19, by
     #: lsq_signw_conv2d on x.float() with the bound rounded into the type (False)
     fp_half_kernel = True
+
+    #: a bf16 / fp16 input in ``train()`` mode (binary fp32 weights, autocast off or set to the input's type) takes the kernels
+    #: forward and backward: ``hip_train._QuantConv2dStepHalf``, whose input gradient is one lsq_signw_conv2d_dgrad_half.
+    #: A switch of its own, independent of ``act_half`` / ``fp_half``.  False: the torch formulation, the default whatever the
+    #: measurement says in the change that adds it
+    hip_train_half = False
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):

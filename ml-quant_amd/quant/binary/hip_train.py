@@ -31,6 +31,16 @@ zero-inserted gradient; every geometry that kernel's plan accepts (groups, dilat
 takes the kernels, and the weight gradient takes ``lsq_train_wgrad`` only where that kernel's stated geometry holds.
 The forward's weight side and activation side (forced scales, moving averages) and the module's plane workspace are
 ``quant.binary.hip_train_common``'s, shared with ``hip_train_linear``; its retention policy is ``HipQuantModule._workspace``.
+
+With ``QuantConv2d.hip_train_half`` (a class attribute, False by default) a bf16 / fp16 input takes a step of its own,
+``_QuantConv2dStepHalf`` -- what a layer is handed under ``torch.autocast('cuda', torch.bfloat16)``:
+forward   ``lsq_act_quant_half`` reads the 16-bit samples as they are (the clamp bound rounded into their type), then
+          ``lsq_xnor_conv2d`` and one rounding of its fp32 result into the type; fp activations: ``lsq_signw_conv2d_half``;
+backward  grad_x is ONE ``lsq_signw_conv2d_dgrad_half`` (liblsq_hip_conv_train_half.so): the 16-bit grad_y as it is against the
+          forward's own weight planes, the straight-through estimator against the 16-bit x in the kernel's epilogue, a 16-bit
+          grad_x -- bit for bit ``lsq_ste_backward(x.float(), lsq_signw_conv2d_dgrad(gy.float())).to(dtype)``.  There is no
+          other route for a 16-bit input, so ``DGRAD_KERNEL`` does not matter here; grad_w and grad_b are computed in fp32
+          from one ``gy.float()`` as in the fp32 step.
 """
 
 from typing import List, Optional
@@ -60,16 +70,43 @@ def _wgrad_geometry(conv) -> bool:
             and conv.padding[0] <= kh - 1 and conv.padding[1] <= kw - 1 and max(kh, kw) <= 8)
 
 
+def _half_supported(conv, x, _hip) -> bool:
+    """The 16-bit step (``hip_train_half``): autocast off or set to the input's type, what the plan of
+    lsq_signw_conv2d_dgrad_half accepts, and the limits of lsq_act_quant_half + lsq_xnor_conv2d (binary activations) or of
+    lsq_signw_conv2d_half (fp activations) -- independent of the eval switches ``act_half`` / ``fp_half``."""
+    if torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') != x.dtype:
+        return False                      # (a 16-bit input under an autocast of another type: torch decides the types)
+    geom = conv._geom_of(x, _hip)
+    if not _hip.signw_conv2d_dgrad_half_supported(geom):      # (a missing library raises: the switch asked for the kernel)
+        return False
+    if x.shape[0] > _hip.CONV_DGRAD_HALF_MAX_SAMPLES or conv.out_channels > 65535:
+        return False
+    if getattr(conv.w_approximate, 'k', 1) > _hip.MAX_PLANES:
+        return False
+    if conv.x_quant == 'fp':
+        return _hip.signw_conv2d_half_supported(geom)
+    if getattr(conv.x_approximate, 'n_planes', 1) > _hip.MAX_PLANES or max(conv.kernel_size) > _hip.MAX_XNOR_KERNEL:
+        return False
+    m = x.shape[1] * x.shape[2] * x.shape[3]
+    if conv.x_quant in ('ls-2', 'ls-T') and (m + conv.act_skip - 1) // conv.act_skip >= _hip.MAX_SOLVER_KEYS:
+        return False
+    return True
+
+
 def supported(conv, x: torch.Tensor) -> bool:
-    """Train-mode forward + backward on the kernels: fp32 4-d CUDA input, binary weights, plain geometry -- and the library
-    built (without it a training run on a GPU host takes the torch formulation; the eval path, by contrast, raises)."""
+    """Train-mode forward + backward on the kernels: fp32 (with ``hip_train_half``: bf16 / fp16) 4-d CUDA input, binary
+    weights, plain geometry -- and the library built (without it a training run on a GPU host takes the torch formulation;
+    the eval path, by contrast, raises)."""
     from quant import _hip
     if not _hip.available():
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and conv.weight.dtype == torch.float32):
+    half = x.dtype in (torch.bfloat16, torch.float16) and conv.hip_train_half
+    if not (x.is_cuda and x.dim() == 4 and (x.dtype == torch.float32 or half) and conv.weight.dtype == torch.float32):
         return False
     if conv.w_quant == 'fp' or conv.padding_mode != 'zeros' or isinstance(conv.padding, str):
         return False
+    if half:
+        return _half_supported(conv, x, _hip)
     if DGRAD_KERNEL:
         # what the plan of lsq_signw_conv2d_dgrad accepts (a missing library raises: the switch asked for the kernel)
         if not _hip.signw_conv2d_dgrad_supported(conv._geom_of(x, _hip)):
@@ -195,6 +232,72 @@ class _QuantConv2dStep(torch.autograd.Function):
         return gx, gw, gb, None
 
 
+class _QuantConv2dStepHalf(torch.autograd.Function):
+    """The step on a bf16 / fp16 input (``hip_train_half``): y and grad_x in the input's type, grad_w and grad_b in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, conv):
+        from quant import _hip
+        x = x.contiguous()
+        n, c, h, w = x.shape
+        alpha = conv._alpha_in(x.dtype)                 # the bound as Tensor.clamp rounds it into the type
+        geom = conv._geom_of(x, _hip)
+        with torch.autocast('cuda', enabled=False):
+            wscales, wbits, wsum = step_weight_planes(conv, weight.detach(), geom, _hip)
+        b = None if bias is None else bias.detach()
+        keep_planes = False
+        if conv.x_quant == 'fp':
+            y = _hip.signw_conv2d_half(x.detach(), alpha, wbits, wscales, b, geom)
+            xscales = None
+        else:
+            k = conv.x_approximate.n_planes
+            keep_planes = WGRAD_KERNEL and ctx.needs_input_grad[1] and _wgrad_geometry(conv)
+            if keep_planes:
+                planes = zero_planes(geom, k, x.device, _hip)
+            else:
+                planes = step_planes(conv, geom, k, x.device, _hip, (geom.pad_h, geom.pad_w, x.dtype))
+            xscales = step_act_quant(conv, x.detach(), geom, planes, _hip, alpha)
+            y32 = torch.empty((n, conv.out_channels) + tuple(_hip.out_hw(geom)), dtype=torch.float32, device=x.device)
+            _hip.xnor_conv2d(planes, k, xscales, wbits, wsum, wscales, b, geom, y32)
+            y = y32.to(x.dtype)                         # one rounding of the fp32 result
+            conv.last_act_scales = xscales
+        ctx.conv, ctx.geom, ctx.alpha = conv, geom, alpha
+        ctx.has_bias = bias is not None
+        empty = x.new_empty(0, dtype=torch.int64)
+        ctx.save_for_backward(x, weight, wscales, xscales if xscales is not None else wscales.new_empty(0),
+                              planes if keep_planes else empty, wbits if ctx.needs_input_grad[0] else empty)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        from quant import _hip
+        conv, geom, alpha = ctx.conv, ctx.geom, ctx.alpha
+        x, weight, wscales, xscales, planes, wbits = ctx.saved_tensors
+        xscales = xscales if xscales.numel() else None
+        gy = gy.to(x.dtype).contiguous()
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        gx = gw = gb = None
+        if need_x:
+            gx = _hip.signw_conv2d_dgrad_half(gy, wbits, wscales, geom, x, xscales, alpha)
+        if need_w or need_b:
+            with torch.autocast('cuda', enabled=False):
+                gy32 = gy.float()
+                if need_b:
+                    gb = gy32.sum(dim=(0, 2, 3))
+                if need_w:
+                    if planes.numel():
+                        gwq = _hip.wgrad(planes, xscales.shape[0], xscales, gy32, geom)
+                    else:
+                        xq = _hip.quant_values(x.float(), xscales, alpha)
+                        gwq = torch.nn.grad.conv2d_weight(xq, weight.shape, gy32, conv.stride, conv.padding, conv.dilation,
+                                                          conv.groups)
+                    gw = _hip.ste_backward(weight.detach(), gwq, wscales, -1.0)
+        return gx, gw, gb, None
+
+
 def train_step_forward(conv, x: torch.Tensor) -> torch.Tensor:
     """``conv(x)`` in train mode through the kernels, differentiable with respect to x, weight and bias."""
+    if x.dtype != torch.float32:
+        return _QuantConv2dStepHalf.apply(x, conv.weight, conv.bias, conv)
     return _QuantConv2dStep.apply(x, conv.weight, conv.bias, conv)
