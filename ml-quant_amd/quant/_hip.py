@@ -5,14 +5,19 @@ device pointers (``tensor.data_ptr()``) and the current HIP stream.  There is no
 eager fallback here: if the library is missing, or a call fails, an exception is raised.
 """
 
+import collections
 import contextlib
 import ctypes
+import functools
 import warnings
 import os
 import threading
 from typing import Optional, Sequence
 
 import torch
+
+from . import _sublibs
+from ._sublibs import ConvGeom, NextLs1, ConvDgradPlan  # noqa: F401  (the mirrors of the C structs: public names of this module)
 
 _LIB_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib')
 # (LSQ_HIP_LIB: developer builds, e.g. -DLSQ_PHASE_CLOCKS)
@@ -29,26 +34,6 @@ XNOR_MFMA_MAX_OUTPUTS = 1 << 30      # lsq_xnor_conv2d: at this many outputs the
 _xnor_limit_warned = set()
 
 
-class ConvGeom(ctypes.Structure):
-    """Mirror of ``lsq_conv_geom``."""
-
-    _fields_ = [(n, ctypes.c_int32) for n in (
-        'N', 'C', 'H', 'W', 'O', 'KH', 'KW', 'stride_h', 'stride_w',
-        'pad_h', 'pad_w', 'dil_h', 'dil_w', 'groups')]
-
-    def key(self):
-        k = self.__dict__.get('_key')             # (make_geom leaves the tuple it was built from: 14 ctypes field reads otherwise)
-        return k if k is not None else tuple(getattr(self, n) for n, _ in self._fields_)
-
-
-class NextLs1(ctypes.Structure):
-    """Mirror of ``lsq_next_ls1``: where a chained convolution leaves the next layer's 1-bit input."""
-
-    _fields_ = [('planes', ctypes.c_void_p), ('sum_units', ctypes.c_void_p), ('pre_scale', ctypes.c_void_p),
-                ('pre_shift', ctypes.c_void_p), ('clamp_alpha', ctypes.c_float), ('pad_h', ctypes.c_int32),
-                ('pad_w', ctypes.c_int32)]
-
-
 class LsqHipError(RuntimeError):
     """A C-ABI call returned a non-zero code."""
 
@@ -57,64 +42,17 @@ def library_path() -> str:
     return _LIB_PATH
 
 
-def _declare(lib):
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    gp = ctypes.POINTER(ConvGeom)
-    lib.lsq_abi_version.restype = i32
-    lib.lsq_error_string.restype = ctypes.c_char_p
-    lib.lsq_error_string.argtypes = [i32]
-    lib.lsq_act_plane_words.restype = i64
-    lib.lsq_act_plane_words.argtypes = [gp]
-    lib.lsq_weight_plane_words.restype = i64
-    lib.lsq_weight_plane_words.argtypes = [gp]
-    lib.lsq_act_quant.restype = i32
-    lib.lsq_act_quant.argtypes = [vp, gp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.lsq_solver_workspace_bytes.restype = i64
-    lib.lsq_solver_workspace_bytes.argtypes = [i64]
-    lib.lsq_sweep_workspace_bytes.restype = i64
-    lib.lsq_sweep_workspace_bytes.argtypes = [i64]
-    lib.lsq_solve_rows.restype = i32
-    lib.lsq_solve_rows.argtypes = [vp, i64, i64, i32, i32, f32, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.lsq_pack_weight.restype = i32
-    lib.lsq_pack_weight.argtypes = [vp, gp, i32, vp, vp, vp, vp]
-    lib.lsq_xnor_conv2d.restype = i32
-    lib.lsq_xnor_conv2d.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, vp, vp]
-    lib.lsq_signw_conv2d.restype = i32
-    lib.lsq_signw_conv2d.argtypes = [vp, f32, vp, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, vp, vp]
-    lib.lsq_signw_weight_bytes.restype = i64
-    lib.lsq_signw_weight_bytes.argtypes = [gp, i32]
-    lib.lsq_signw_prepare_weight.restype = i32
-    lib.lsq_signw_prepare_weight.argtypes = [vp, i32, gp, vp, vp]
-    lib.lsq_pool_bias_relu_nhwc.restype = i32
-    lib.lsq_pool_bias_relu_nhwc.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]
-    lib.lsq_pointwise_conv.restype = i32
-    lib.lsq_pointwise_conv.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]
-    for hook in ('lsq_debug_xnor_impl', 'lsq_debug_force_streaming', 'lsq_debug_fused_mode'):     # include/lsq_hip_debug.h
-        getattr(lib, hook).restype = i32
-        getattr(lib, hook).argtypes = [i32]
-    lib.lsq_xnor_conv2d_chain.restype = i32
-    lib.lsq_xnor_conv2d_chain.argtypes = [vp, vp, vp, f32, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, ctypes.POINTER(NextLs1), vp, vp]
-    lib.lsq_quant_values.restype = i32
-    lib.lsq_quant_values.argtypes = [vp, i64, i64, i32, vp, f32, vp, vp]
-    lib.lsq_ste_backward.restype = i32
-    lib.lsq_ste_backward.argtypes = [vp, vp, i64, i64, i32, vp, f32, vp, vp]
-    lib.lsq_debug_solver_trace.restype = i32
-    lib.lsq_debug_solver_trace.argtypes = [vp]
-    lib.lsq_stem_conv_pool.restype = i32
-    lib.lsq_stem_conv_pool.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
-
-
-def _load(path, make_dir, declare, version_symbol, version, soname):
+def _load(path, make_dir, prototypes, version_symbol, version, soname):
     """Load one of the C-ABI libraries: ``path`` must exist (no fallback: a missing library is an error that says how to
-    build it, ``make -C ml-quant_amd/<make_dir>``), ``declare(handle)`` sets the prototypes, and ``version_symbol()`` must
-    return ``version``.  Loads are serialized; a ``*_lib()`` function keeps the handle in its own module global."""
+    build it, ``make -C ml-quant_amd/<make_dir>``), its functions get the ``prototypes`` of quant/_sublibs.py, and
+    ``version_symbol()`` must return ``version``.  Loads are serialized; the caller keeps the handle."""
     with _lock:
         if not os.path.exists(path):
             raise LsqHipError(
                 f'{path} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                 f'(or `make -C ml-quant_amd/{make_dir}`). The HIP path has no fallback.')
         handle = ctypes.CDLL(path)
-        declare(handle)
+        _sublibs.apply_prototypes(handle, prototypes)
         if getattr(handle, version_symbol)() != version:
             raise LsqHipError(f'{soname} ABI version mismatch')
         return handle
@@ -124,7 +62,8 @@ def lib():
     """Load (once) and return the C-ABI library; raises if it has not been built."""
     global _lib
     if _lib is None:
-        _lib = _load(_LIB_PATH, 'csrc', _declare, 'lsq_abi_version', ABI_VERSION, 'liblsq_hip.so')
+        prototypes = {**_sublibs.MAIN_PROTOTYPES['lsq_hip.h'], **_sublibs.MAIN_PROTOTYPES['lsq_hip_debug.h']}
+        _lib = _load(_LIB_PATH, 'csrc', prototypes, 'lsq_abi_version', ABI_VERSION, 'liblsq_hip.so')
     return _lib
 
 
@@ -250,7 +189,7 @@ class _Timed:
             _timing.setdefault(self.name, []).append((self.s, self.e, self.nbytes))
 
 
-_ws_cache = {}
+_ws_caches = collections.defaultdict(dict)      # {cache name: {(device, stream): buffer}}: one cache per kernel family, none shared
 _WS_CACHE_MAX = 16      # (device, stream) entries kept per cache: streams come and go (one per captured graph)
 
 
@@ -274,9 +213,10 @@ def _ws_bytes(fn: str, rows: int) -> int:
     return need
 
 
-def _stream_buffer(cache: dict, need: int, device, zeroed: bool = False) -> torch.Tensor:
-    """The uint8 buffer of at least ``need`` bytes that ``cache`` keeps for (device, its current stream), grown on demand
-    (``zeroed``: a new one starts as zeros) -- kernels of one stream run in order, so sharing it between calls is safe."""
+def _stream_buffer(name: str, need: int, device, zeroed: bool = False) -> torch.Tensor:
+    """The uint8 buffer of at least ``need`` bytes that the cache ``name`` keeps for (device, its current stream), grown on
+    demand (``zeroed``: a new one starts as zeros) -- kernels of one stream run in order, so sharing it between calls is safe."""
+    cache = _ws_caches[name]
     device = torch.device(device)
     if device.index is None:
         device = torch.device('cuda', torch.cuda.current_device())
@@ -291,15 +231,18 @@ def _stream_buffer(cache: dict, need: int, device, zeroed: bool = False) -> torc
 def solver_workspace(rows: int, device) -> torch.Tensor:
     """Scratch for the LS2/LST solve (slot records passed from the sweep to the solve kernel); cached per
     (device, stream) and grown on demand."""
-    return _stream_buffer(_ws_cache, _ws_bytes('lsq_solver_workspace_bytes', rows), device)
+    return _stream_buffer('solver', _ws_bytes('lsq_solver_workspace_bytes', rows), device)
 
-
-_sweep_ws_cache = {}
 
 def sweep_workspace(rows: int, device) -> torch.Tensor:
     """Row workspace of the ls-1 / gf-k sweeps (partial sums + arrival counters of rows shared by several workgroups):
     any content (the arrival slots carry a per-launch epoch); cached per (device, stream) like the solver's."""
-    return _stream_buffer(_sweep_ws_cache, _ws_bytes('lsq_sweep_workspace_bytes', rows), device, zeroed=True)
+    return _stream_buffer('sweep', _ws_bytes('lsq_sweep_workspace_bytes', rows), device, zeroed=True)
+
+
+def _ws_args(ws: Optional[torch.Tensor]):
+    """The (pointer, bytes) arguments of an optional workspace."""
+    return (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
 
 
 def act_quant(x: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: int, alpha: float,
@@ -315,8 +258,8 @@ def act_quant(x: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: int, a
     with _on(x), (_Timed('lsq_act_quant', geom.N * (4 * m + k * m // 8), 0, f'C{geom.C}_H{geom.H}') if _timing is not None else _UNTIMED):
         check(lib().lsq_act_quant(x.data_ptr(), ctypes.byref(geom), scheme, k, skip, float(alpha),
                                   None if pre is None else pre[0].data_ptr(), None if pre is None else pre[1].data_ptr(),
-                                  ptr(forced), planes.data_ptr(), scales.data_ptr(), ptr(ws),
-                                  0 if ws is None else ws.numel(), stream_ptr(x.device)), 'lsq_act_quant')
+                                  ptr(forced), planes.data_ptr(), scales.data_ptr(), *_ws_args(ws), stream_ptr(x.device)),
+              'lsq_act_quant')
 
 
 def solve_rows(rows: torch.Tensor, skip: int, ternary: bool, alpha: float = -1.0):
@@ -615,38 +558,55 @@ def ste_backward(x: torch.Tensor, grad_q: torch.Tensor, scales: Optional[torch.T
     return out
 
 
-# ---- the training library (include/lsq_hip_train.h): a second shared object, loaded on first use
-_TRAIN_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_train.so')
-TRAIN_ABI_VERSION = 1
-_train_lib = None
+# ---- the libraries beside liblsq_hip.so, one shared object per kernel family, each loaded on first use.  They are the entries
+# of quant/_sublibs.py.  A new family is: an entry there (its prototypes are held against the header by
+# tests/test_sublib_table_host.py), csrc/<dir>/Makefile that includes csrc/sublib.mk, include/lsq_hip_<dir>.h, and one line
+# of public names below; __graft_entry__.build() makes and checks every entry of the table.
+def _sublib_path(name: str) -> str:
+    return os.path.join(_LIB_DIR, _sublibs.soname(_sublibs.BY_DIR[name]))
 
 
-def train_library_path() -> str:
-    return _TRAIN_LIB_PATH
+class _Handles(dict):
+    """{dir of the entry: its loaded library}; a miss loads the library, which raises if it has not been built (no fallback,
+    as ``lib()``)."""
+
+    def __missing__(self, name):
+        s = _sublibs.BY_DIR[name]
+        handle = self[name] = _load(_sublib_path(name), 'csrc/' + name, s.prototypes, s.version_symbol, s.version,
+                                    _sublibs.soname(s))
+        return handle
 
 
-def _declare_train(handle):
-    vp, i32, gp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ConvGeom)
-    handle.lsq_train_abi_version.restype = i32
-    handle.lsq_train_abi_version.argtypes = []
-    handle.lsq_train_wgrad_workspace_bytes.restype = ctypes.c_size_t
-    handle.lsq_train_wgrad_workspace_bytes.argtypes = [gp, i32]
-    handle.lsq_train_wgrad.restype = i32
-    handle.lsq_train_wgrad.argtypes = [vp, i32, vp, vp, gp, vp, vp, ctypes.c_size_t, vp]
+_handles = _Handles()
 
 
-def train_lib():
-    """Load (once) and return the training library; raises if it has not been built (no fallback, as ``lib()``)."""
-    global _train_lib
-    if _train_lib is None:
-        _train_lib = _load(_TRAIN_LIB_PATH, 'csrc/train', _declare_train,
-                           'lsq_train_abi_version', TRAIN_ABI_VERSION, 'liblsq_hip_train.so')
-    return _train_lib
+def _sublib(name: str):
+    """(loader, library_path, ABI version) of the entry ``name``: ``loader()`` is ``_handles[name]`` and no more, so that a
+    warm call costs one dict lookup -- no lock, no Python frame."""
+    return functools.partial(_handles.__getitem__, name), functools.partial(_sublib_path, name), _sublibs.BY_DIR[name].version
 
 
-_wgrad_ws_cache = {}
+train_lib, train_library_path, TRAIN_ABI_VERSION = _sublib('train')
+linear_lib, linear_library_path, LINEAR_ABI_VERSION = _sublib('linear')
+linear_fp_lib, linear_fp_library_path, LINEAR_FP_ABI_VERSION = _sublib('linear_fp')
+linear_train_lib, linear_train_library_path, LINEAR_TRAIN_ABI_VERSION = _sublib('linear_train')
+linear_wgrad_lib, linear_wgrad_library_path, LINEAR_WGRAD_ABI_VERSION = _sublib('linear_wgrad')
+linear_half_lib, linear_half_library_path, LINEAR_HALF_ABI_VERSION = _sublib('linear_half')
+linear_act_half_lib, linear_act_half_library_path, LINEAR_ACT_HALF_ABI_VERSION = _sublib('linear_act_half')
+linear_act_solve_lib, linear_act_solve_library_path, LINEAR_ACT_SOLVE_ABI_VERSION = _sublib('linear_act_solve')
+conv_act_half_lib, conv_act_half_library_path, CONV_ACT_HALF_ABI_VERSION = _sublib('conv_act_half')
+conv_half_lib, conv_half_library_path, CONV_HALF_ABI_VERSION = _sublib('conv_half')
+conv_train_lib, conv_train_library_path, CONV_TRAIN_ABI_VERSION = _sublib('conv_train')
+conv_train_half_lib, conv_train_half_library_path, CONV_TRAIN_HALF_ABI_VERSION = _sublib('conv_train_half')
+
+LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
+LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
+LINEAR_WGRAD_MAX_SAMPLES = 65535    # lsq_linear_signx_wgrad: N <= 65535 (the limit of lsq_quant_values)
+LINEAR_HALF_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}     # LSQ_DTYPE_*
+CONV_DGRAD_HALF_MAX_SAMPLES = 65535    # lsq_signw_conv2d_dgrad_half with x: N <= 65535 (the limit of lsq_ste_backward)
 
 
+# ---- the training library (include/lsq_hip_train.h)
 def wgrad(planes: torch.Tensor, kx: int, xscales: torch.Tensor, gy: torch.Tensor, geom: ConvGeom) -> torch.Tensor:
     """grad_wq [O, C, KH, KW] = conv2d_weight(x_q, grad_y) with x_q = sum_p xscales[p][n] (2 bit_p - 1) read from the
     activation planes ``planes`` (lsq_train_wgrad), on the current stream.  The split-K slabs live in a workspace cached
@@ -656,87 +616,97 @@ def wgrad(planes: torch.Tensor, kx: int, xscales: torch.Tensor, gy: torch.Tensor
         raise TypeError('activation planes are a contiguous int64 tensor')
     tl = train_lib()
     need = int(tl.lsq_train_wgrad_workspace_bytes(ctypes.byref(geom), int(kx)))
-    ws = _stream_buffer(_wgrad_ws_cache, need, gy.device) if need else None
+    ws = _stream_buffer('wgrad', need, gy.device) if need else None
     out = torch.empty((geom.O, geom.C, geom.KH, geom.KW), dtype=torch.float32, device=gy.device)
     ho, wo = out_hw(geom)
     with _on(gy), _Timed('lsq_train_wgrad', 4 * gy.numel() + 8 * kx * act_plane_words(geom) + 4 * out.numel(),
                          2 * geom.N * ho * wo * geom.O * geom.C * geom.KH * geom.KW):
         check(tl.lsq_train_wgrad(planes.data_ptr(), int(kx), xscales.data_ptr(), gy.data_ptr(), ctypes.byref(geom),
-                                 out.data_ptr(), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(gy.device)),
-              'lsq_train_wgrad')
+                                 out.data_ptr(), *_ws_args(ws), stream_ptr(gy.device)), 'lsq_train_wgrad')
     return out
 
 
-def _check_linear(what: str, dims: dict, fp32: dict, int64: Optional[dict] = None, int32: Optional[dict] = None,
-                  bad: bool = False, wplanes: Optional[tuple] = None, mismatch=None,
-                  bias: Optional[torch.Tensor] = None) -> None:
-    """The host-side operand checks of the linear entry points (``what`` names one), in one order; the first that fails
-    raises.  TypeError: an operand of ``fp32`` / ``int64`` / ``int32`` = {name: tensor}, or ``bias``, of another dtype.  Then
-    ValueError ``'<what>: ...'``:
-      * operands that are not ``contiguous``;
-      * ``bad sizes``: an entry of ``dims`` = {name: size} that is not positive, or ``bad`` (the caller's element counts
-        against the dims);
-      * operands that ``do not match``: ``wplanes`` = (wbits, wscales, F, O), the sign planes / scales [kw, O] lsq_pack_weight
-        took and wrote for (O, F, 1, 1); then ``mismatch()``, the caller's own (what does not match, or None);
-      * a ``bias`` of other than ``dims['O']`` elements;
-      * last -- so that every check above can be reached with CPU tensors -- operands not all on the same ``cuda device``."""
-    if bias is not None:
-        fp32 = dict(fp32, bias=bias)
+# ---- the host-side operand checks of the entry points below (``what`` names one), in one order; the first that fails raises
+def _check_half(what: str, name: str, t: torch.Tensor) -> None:
+    """TypeError unless the 16-bit operand ``t`` is bf16 or fp16: the first check of every 16-bit entry point."""
+    if t.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f'{what}: {name} must be a bfloat16 or float16 tensor, got {t.dtype}')
+
+
+def _check_dtypes(what: str, fp32: dict, int64: Optional[dict] = None, int32: Optional[dict] = None) -> list:
+    """TypeError for an operand of ``fp32`` / ``int64`` / ``int32`` = {name: tensor} of another dtype; returns the tensors."""
     groups = ((torch.float32, fp32), (torch.int64, int64 or {}), (torch.int32, int32 or {}))
     for dtype, named in groups:
         wrong = [name for name, t in named.items() if t.dtype != dtype]
         if wrong:
             raise TypeError(f'{what}: {", ".join(wrong)} must be {dtype} tensors')
-    tensors = [t for _, named in groups for t in named.values()]
+    return [t for _, named in groups for t in named.values()]
+
+
+def _check_placement(what: str, tensors: Sequence[torch.Tensor], problem=None) -> None:
+    """ValueError ``'<what>: ...'`` for operands that are not ``contiguous``; then with the text ``problem()`` returns (the
+    caller's own checks of sizes and of what must match, None: nothing to say); last -- so that every check above can be
+    reached with CPU tensors, no library loaded -- for operands not all on the same ``cuda device``."""
     if any(not t.is_contiguous() for t in tensors):
         raise ValueError(f'{what}: operands must be contiguous')
-    if bad or min(dims.values()) <= 0:
-        raise ValueError(f'{what}: bad sizes ' + ' '.join(f'{name}={v}' for name, v in dims.items()) + ' for '
-                         + ', '.join(f'{name} of {t.numel()}' for name, t in fp32.items()) + ' elements')
-    if wplanes is not None:
-        wbits, wscales, F, O = wplanes
-        if wscales.dim() != 2 or wscales.shape[1] != O \
-                or wbits.numel() != wscales.shape[0] * ((F + 63) // 64) * ((O + 15) // 16 * 16):
-            raise ValueError(f'{what}: weight planes / scales do not match (kw, F, O)')
-    problem = None if mismatch is None else mismatch()
-    if problem is not None:
-        raise ValueError(f'{what}: {problem} do not match')
-    if bias is not None and bias.numel() != dims['O']:
-        raise ValueError(f'{what}: bias must have O elements')
+    text = None if problem is None else problem()
+    if text is not None:
+        raise ValueError(f'{what}: {text}')
     dev = tensors[0].device
     if dev.type != 'cuda' or any(t.device != dev for t in tensors):
         raise ValueError(f'{what}: every operand on the same cuda device')
 
 
-# ---- the linear-layer library (include/lsq_hip_linear.h): a third shared object, loaded on first use
-_LINEAR_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear.so')
-LINEAR_ABI_VERSION = 1
-LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
-LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
-_linear_lib = None
+def _check_operands(what: str, fp32: dict, int64: Optional[dict] = None, int32: Optional[dict] = None,
+                    half: Sequence[torch.Tensor] = (), problem=None) -> None:
+    """``_check_dtypes``, then ``_check_placement`` of those operands and of ``half`` (the 16-bit ones: ``_check_half`` is the
+    caller's, in front).  An entry point with a dtype check of its own in between calls the two itself."""
+    _check_placement(what, [*half, *_check_dtypes(what, fp32, int64, int32)], problem)
 
 
-def linear_library_path() -> str:
-    return _LINEAR_LIB_PATH
+def _check_linear(what: str, dims: dict, fp32: dict, int64: Optional[dict] = None, int32: Optional[dict] = None,
+                  bad: bool = False, wplanes: Optional[tuple] = None, mismatch=None,
+                  bias: Optional[torch.Tensor] = None) -> None:
+    """``_check_operands`` (``bias`` is one of ``fp32``) with the linear entry points' own checks between contiguity and device:
+      * ``bad sizes``: an entry of ``dims`` = {name: size} that is not positive, or ``bad`` (the caller's element counts
+        against the dims);
+      * operands that ``do not match``: ``wplanes`` = (wbits, wscales, F, O), the sign planes / scales [kw, O] lsq_pack_weight
+        took and wrote for (O, F, 1, 1); then ``mismatch()``, the caller's own (what does not match, or None);
+      * a ``bias`` of other than ``dims['O']`` elements."""
+    if bias is not None:
+        fp32 = dict(fp32, bias=bias)
+
+    def problem():
+        if bad or min(dims.values()) <= 0:
+            return ('bad sizes ' + ' '.join(f'{name}={v}' for name, v in dims.items()) + ' for '
+                    + ', '.join(f'{name} of {t.numel()}' for name, t in fp32.items()) + ' elements')
+        if wplanes is not None:
+            wbits, wscales, F, O = wplanes
+            if wscales.dim() != 2 or wscales.shape[1] != O \
+                    or wbits.numel() != wscales.shape[0] * ((F + 63) // 64) * ((O + 15) // 16 * 16):
+                return 'weight planes / scales do not match (kw, F, O)'
+        subject = None if mismatch is None else mismatch()
+        if subject is not None:
+            return f'{subject} do not match'
+        if bias is not None and bias.numel() != dims['O']:
+            return 'bias must have O elements'
+
+    _check_operands(what, fp32, int64, int32, problem=problem)
 
 
-def _declare_linear(handle):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    handle.lsq_linear_abi_version.restype = i32
-    handle.lsq_linear_abi_version.argtypes = []
-    handle.lsq_linear_xnor.restype = i32
-    handle.lsq_linear_xnor.argtypes = [vp, i32, vp, i64, vp, vp, i32, vp, vp, i64, i64, i64, vp, vp]
+def _geom_matches_gy(geom: ConvGeom, gy: torch.Tensor) -> bool:
+    """Whether the forward geometry is a valid one and ``gy`` has the shape of its output."""
+    return (min(geom.N, geom.C, geom.H, geom.W, geom.O, geom.KH, geom.KW, geom.groups, geom.stride_h, geom.stride_w,
+                geom.dil_h, geom.dil_w) >= 1 and min(geom.pad_h, geom.pad_w) >= 0 and geom.C % geom.groups == 0
+            and geom.O % geom.groups == 0 and tuple(gy.shape) == (geom.N, geom.O) + tuple(out_hw(geom)))
 
 
-def linear_lib():
-    """Load (once) and return the linear-layer library; raises if it has not been built (no fallback, as ``lib()``)."""
-    global _linear_lib
-    if _linear_lib is None:
-        _linear_lib = _load(_LINEAR_LIB_PATH, 'csrc/linear', _declare_linear,
-                            'lsq_linear_abi_version', LINEAR_ABI_VERSION, 'liblsq_hip_linear.so')
-    return _linear_lib
+def _signw_plane_words(geom: ConvGeom) -> int:
+    """int64 words of one sign-weight plane of ``geom``: KH * KW * ceil(C/g / 64) * g * ceil16(O/g)."""
+    return geom.KH * geom.KW * ((geom.C // geom.groups + 63) // 64) * geom.groups * ((geom.O // geom.groups + 15) // 16 * 16)
 
 
+# ---- the linear-layer library (include/lsq_hip_linear.h)
 def linear_xnor(planes: torch.Tensor, kx: int, xscales: torch.Tensor, rows_per_scale: int, wbits: torch.Tensor,
                 wsum: torch.Tensor, wscales: torch.Tensor, bias: Optional[torch.Tensor], M: int, F: int, O: int) -> torch.Tensor:
     """y [M, O] = F.linear(x_q, w_q, bias) from sign planes (lsq_linear_xnor): ``planes`` / ``xscales`` [kx, M / rows_per_scale]
@@ -761,34 +731,7 @@ def linear_xnor(planes: torch.Tensor, kx: int, xscales: torch.Tensor, rows_per_s
     return y
 
 
-# ---- the fp-activation linear-layer library (include/lsq_hip_linear_fp.h): a fourth shared object, loaded on first use
-_LINEAR_FP_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_fp.so')
-LINEAR_FP_ABI_VERSION = 1
-_linear_fp_lib = None
-
-
-def linear_fp_library_path() -> str:
-    return _LINEAR_FP_LIB_PATH
-
-
-def _declare_linear_fp(handle):
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    handle.lsq_linear_fp_abi_version.restype = i32
-    handle.lsq_linear_fp_abi_version.argtypes = []
-    handle.lsq_linear_signw.restype = i32
-    handle.lsq_linear_signw.argtypes = [vp, f32, vp, i32, vp, vp, i64, i64, i64, vp, vp]
-
-
-def linear_fp_lib():
-    """Load (once) and return the fp-activation linear-layer library; raises if it has not been built (no fallback, as
-    ``lib()``)."""
-    global _linear_fp_lib
-    if _linear_fp_lib is None:
-        _linear_fp_lib = _load(_LINEAR_FP_LIB_PATH, 'csrc/linear_fp', _declare_linear_fp,
-                               'lsq_linear_fp_abi_version', LINEAR_FP_ABI_VERSION, 'liblsq_hip_linear_fp.so')
-    return _linear_fp_lib
-
-
+# ---- the fp-activation linear-layer library (include/lsq_hip_linear_fp.h)
 def linear_signw(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: torch.Tensor, bias: Optional[torch.Tensor],
                  M: int, F: int, O: int) -> torch.Tensor:
     """y [M, O] = F.linear(clamp(x), w_q, bias) for fp32 rows ``x`` [M, F] (any 4-byte-aligned data pointer) and the sign
@@ -807,39 +750,7 @@ def linear_signw(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: to
     return y
 
 
-# ---- the linear-layer training library (include/lsq_hip_linear_train.h): a fifth shared object, loaded on first use
-_LINEAR_TRAIN_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_train.so')
-LINEAR_TRAIN_ABI_VERSION = 1
-_linear_train_lib = None
-
-
-def linear_train_library_path() -> str:
-    return _LINEAR_TRAIN_LIB_PATH
-
-
-def _declare_linear_train(handle):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    handle.lsq_linear_train_abi_version.restype = i32
-    handle.lsq_linear_train_abi_version.argtypes = []
-    handle.lsq_linear_signw_dgrad_workspace_bytes.restype = ctypes.c_size_t
-    handle.lsq_linear_signw_dgrad_workspace_bytes.argtypes = [i32, i64, i64]
-    handle.lsq_linear_signw_dgrad.restype = i32
-    handle.lsq_linear_signw_dgrad.argtypes = [vp, vp, i32, vp, i64, i64, i64, vp, vp, ctypes.c_size_t, vp]
-
-
-def linear_train_lib():
-    """Load (once) and return the linear-layer training library; raises if it has not been built (no fallback, as
-    ``lib()``)."""
-    global _linear_train_lib
-    if _linear_train_lib is None:
-        _linear_train_lib = _load(_LINEAR_TRAIN_LIB_PATH, 'csrc/linear_train', _declare_linear_train,
-                                  'lsq_linear_train_abi_version', LINEAR_TRAIN_ABI_VERSION, 'liblsq_hip_linear_train.so')
-    return _linear_train_lib
-
-
-_dgrad_ws_cache = {}
-
-
+# ---- the linear-layer training library (include/lsq_hip_linear_train.h)
 def linear_signw_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Tensor, M: int, F: int, O: int) -> torch.Tensor:
     """gx [M, F] = gy @ w_q for fp32 gradient rows ``gy`` [M, O] (any 4-byte-aligned data pointer) and the sign planes
     ``wbits`` / scales ``wscales`` [kw, O] lsq_pack_weight took and wrote for (O, F, 1, 1) -- the forward's own operands
@@ -851,51 +762,16 @@ def linear_signw_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Ten
     kw, nw, opad, dev = wscales.shape[0], (F + 63) // 64, (O + 15) // 16 * 16, gy.device
     tl = linear_train_lib()
     need = int(tl.lsq_linear_signw_dgrad_workspace_bytes(kw, F, O))
-    ws = _stream_buffer(_dgrad_ws_cache, need, dev) if need else None
+    ws = _stream_buffer('linear_dgrad', need, dev) if need else None
     gx = torch.empty((M, F), dtype=torch.float32, device=dev)
     with _on(gx), _Timed('lsq_linear_signw_dgrad', 4 * M * O * kw + 8 * kw * nw * opad + 2 * need + 4 * M * F,
                          2 * 2 * M * F * O * kw):       # bf16 FLOPs: the hi and the lo pass of every plane
         check(tl.lsq_linear_signw_dgrad(gy.data_ptr(), wbits.data_ptr(), kw, wscales.data_ptr(), M, F, O, gx.data_ptr(),
-                                        ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev)),
-              'lsq_linear_signw_dgrad')
+                                        *_ws_args(ws), stream_ptr(dev)), 'lsq_linear_signw_dgrad')
     return gx
 
 
-# ---- the linear layer's weight-gradient library (include/lsq_hip_linear_wgrad.h): a sixth shared object, loaded on first use
-_LINEAR_WGRAD_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_wgrad.so')
-LINEAR_WGRAD_ABI_VERSION = 1
-LINEAR_WGRAD_MAX_SAMPLES = 65535    # lsq_linear_signx_wgrad: N <= 65535 (the limit of lsq_quant_values)
-_linear_wgrad_lib = None
-
-
-def linear_wgrad_library_path() -> str:
-    return _LINEAR_WGRAD_LIB_PATH
-
-
-def _declare_linear_wgrad(handle):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    handle.lsq_linear_wgrad_abi_version.restype = i32
-    handle.lsq_linear_wgrad_abi_version.argtypes = []
-    handle.lsq_linear_signx_wgrad_workspace_bytes.restype = ctypes.c_size_t
-    handle.lsq_linear_signx_wgrad_workspace_bytes.argtypes = [i32, i64, i64, i64, i64]
-    handle.lsq_linear_signx_wgrad.restype = i32
-    handle.lsq_linear_signx_wgrad.argtypes = [vp, vp, i32, vp, ctypes.c_float, i64, i64, i64, i64, vp, vp,
-                                              ctypes.c_size_t, vp]
-
-
-def linear_wgrad_lib():
-    """Load (once) and return the linear layer's weight-gradient library; raises if it has not been built (no fallback, as
-    ``lib()``)."""
-    global _linear_wgrad_lib
-    if _linear_wgrad_lib is None:
-        _linear_wgrad_lib = _load(_LINEAR_WGRAD_LIB_PATH, 'csrc/linear_wgrad', _declare_linear_wgrad,
-                                  'lsq_linear_wgrad_abi_version', LINEAR_WGRAD_ABI_VERSION, 'liblsq_hip_linear_wgrad.so')
-    return _linear_wgrad_lib
-
-
-_linear_wgrad_ws_cache = {}
-
-
+# ---- the linear layer's weight-gradient library (include/lsq_hip_linear_wgrad.h)
 def linear_signx_wgrad(gy: torch.Tensor, x: torch.Tensor, xscales: torch.Tensor, alpha: float, N: int, T: int, F: int,
                        O: int) -> torch.Tensor:
     """gwq [O, F] = gy^T @ x_q for fp32 gradient rows ``gy`` [N * T, O] (any 4-byte-aligned data pointer), the layer's input
@@ -910,50 +786,16 @@ def linear_signx_wgrad(gy: torch.Tensor, x: torch.Tensor, xscales: torch.Tensor,
     kx, dev = xscales.shape[0], gy.device
     wl = linear_wgrad_lib()
     need = int(wl.lsq_linear_signx_wgrad_workspace_bytes(kx, N, T, F, O))
-    ws = _stream_buffer(_linear_wgrad_ws_cache, need, dev) if need else None
+    ws = _stream_buffer('linear_wgrad', need, dev) if need else None
     gwq = torch.empty((O, F), dtype=torch.float32, device=dev)
     with _on(gwq), _Timed('lsq_linear_signx_wgrad', 4 * M * O + 4 * M * F + 4 * kx * N + 2 * need + 4 * O * F,
                           2 * 2 * M * F * O * kx):       # bf16 FLOPs: the hi and the lo pass of every plane
         check(wl.lsq_linear_signx_wgrad(gy.data_ptr(), x.data_ptr(), kx, xscales.data_ptr(), float(alpha), N, T, F, O,
-                                        gwq.data_ptr(), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev)),
-              'lsq_linear_signx_wgrad')
+                                        gwq.data_ptr(), *_ws_args(ws), stream_ptr(dev)), 'lsq_linear_signx_wgrad')
     return gwq
 
 
-# ---- the 16-bit-activation linear-layer library (include/lsq_hip_linear_half.h): a seventh shared object, loaded on first use
-_LINEAR_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_half.so')
-LINEAR_HALF_ABI_VERSION = 1
-LINEAR_HALF_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}     # LSQ_DTYPE_*
-_linear_half_lib = None
-
-
-def linear_half_library_path() -> str:
-    return _LINEAR_HALF_LIB_PATH
-
-
-def _declare_linear_half(handle):
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    handle.lsq_linear_half_abi_version.restype = i32
-    handle.lsq_linear_half_abi_version.argtypes = []
-    handle.lsq_linear_signw_half_workspace_bytes.restype = i64
-    handle.lsq_linear_signw_half_workspace_bytes.argtypes = [i64, i64, i32, i32]
-    handle.lsq_linear_signw_half.restype = i32
-    handle.lsq_linear_signw_half.argtypes = [vp, i32, f32, vp, i32, vp, vp, i64, i64, i64, vp, i32, vp, ctypes.c_size_t, vp]
-
-
-def linear_half_lib():
-    """Load (once) and return the 16-bit-activation linear-layer library; raises if it has not been built (no fallback, as
-    ``lib()``)."""
-    global _linear_half_lib
-    if _linear_half_lib is None:
-        _linear_half_lib = _load(_LINEAR_HALF_LIB_PATH, 'csrc/linear_half', _declare_linear_half,
-                                 'lsq_linear_half_abi_version', LINEAR_HALF_ABI_VERSION, 'liblsq_hip_linear_half.so')
-    return _linear_half_lib
-
-
-_linear_half_ws_cache = {}
-
-
+# ---- the 16-bit-activation linear-layer library (include/lsq_hip_linear_half.h)
 def linear_signw_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: torch.Tensor, bias: Optional[torch.Tensor],
                       M: int, F: int, O: int, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """y [M, O] = F.linear(x.clamp(-alpha, alpha), w_q, bias) for bf16 / fp16 rows ``x`` [M, F] (any 2-byte-aligned data
@@ -964,8 +806,7 @@ def linear_signw_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscale
     (device, stream) like the solver's (rewritten by every call; kernels of one stream run in order)."""
     M, F, O = int(M), int(F), int(O)
     out_dtype = x.dtype if out_dtype is None else out_dtype
-    if x.dtype not in (torch.bfloat16, torch.float16):
-        raise TypeError(f'lsq_linear_signw_half: x must be a bfloat16 or float16 tensor, got {x.dtype}')
+    _check_half('lsq_linear_signw_half', 'x', x)
     if out_dtype not in (torch.float32, x.dtype):
         raise TypeError(f'lsq_linear_signw_half: out_dtype must be torch.float32 or {x.dtype}, got {out_dtype}')
     _check_linear('lsq_linear_signw_half', {'M': M, 'F': F, 'O': O}, {'wscales': wscales}, {'wbits': wbits},
@@ -979,46 +820,17 @@ def linear_signw_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscale
     hl = linear_half_lib()
     xdt, ydt = LINEAR_HALF_DTYPES[x.dtype], LINEAR_HALF_DTYPES[out_dtype]
     need = int(hl.lsq_linear_signw_half_workspace_bytes(M, O, kw, ydt))
-    ws = _stream_buffer(_linear_half_ws_cache, need, dev) if need else None
+    ws = _stream_buffer('linear_half', need, dev) if need else None
     y = torch.empty((M, O), dtype=out_dtype, device=dev)
     launches = (kw + 1) // 2                         # (the fp32 sum is read back by every launch after the first)
     with _on(y), _Timed('lsq_linear_signw_half', 2 * M * F * launches + 8 * kw * nw * opad + 8 * M * O * (launches - 1)
                         + y.element_size() * M * O, 2 * M * F * O * kw):      # 16-bit FLOPs: one pass per plane
         check(hl.lsq_linear_signw_half(x.data_ptr(), xdt, float(alpha), wbits.data_ptr(), kw, wscales.data_ptr(), ptr(bias),
-                                       M, F, O, y.data_ptr(), ydt, ptr(ws), 0 if ws is None else ws.numel(),
-                                       stream_ptr(dev)), 'lsq_linear_signw_half')
+                                       M, F, O, y.data_ptr(), ydt, *_ws_args(ws), stream_ptr(dev)), 'lsq_linear_signw_half')
     return y
 
 
-# ---- the 16-bit activation quantizer library (include/lsq_hip_linear_act_half.h): an eighth shared object, loaded on first use
-_LINEAR_ACT_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_act_half.so')
-LINEAR_ACT_HALF_ABI_VERSION = 1
-_linear_act_half_lib = None
-
-
-def linear_act_half_library_path() -> str:
-    return _LINEAR_ACT_HALF_LIB_PATH
-
-
-def _declare_linear_act_half(handle):
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    handle.lsq_linear_act_half_abi_version.restype = i32
-    handle.lsq_linear_act_half_abi_version.argtypes = []
-    handle.lsq_linear_act_quant_half.restype = i32
-    handle.lsq_linear_act_quant_half.argtypes = [vp, i32, i64, i64, i32, i32, f32, vp, vp, vp, vp]
-
-
-def linear_act_half_lib():
-    """Load (once) and return the 16-bit activation quantizer library; raises if it has not been built (no fallback, as
-    ``lib()``)."""
-    global _linear_act_half_lib
-    if _linear_act_half_lib is None:
-        _linear_act_half_lib = _load(_LINEAR_ACT_HALF_LIB_PATH, 'csrc/linear_act_half', _declare_linear_act_half,
-                                     'lsq_linear_act_half_abi_version', LINEAR_ACT_HALF_ABI_VERSION,
-                                     'liblsq_hip_linear_act_half.so')
-    return _linear_act_half_lib
-
-
+# ---- the 16-bit activation quantizer library (include/lsq_hip_linear_act_half.h)
 def linear_act_quant_half(x: torch.Tensor, scheme: int, k: int, alpha: float, planes: torch.Tensor, scales: torch.Tensor,
                           forced: Optional[torch.Tensor] = None) -> None:
     """Sign planes and scales of the bf16 / fp16 rows ``x`` [N, L] (any 2-byte-aligned data pointer) into ``planes`` (int64,
@@ -1027,26 +839,20 @@ def linear_act_quant_half(x: torch.Tensor, scheme: int, k: int, alpha: float, pl
     (as Tensor.clamp rounds it), negative for none; ``forced`` [k, N] fp32: scales to use instead of computing them --
     required for ls-2 / ls-T, whose free-running solve is lsq_act_quant's."""
     scheme, k = int(scheme), int(k)
-    if x.dtype not in (torch.bfloat16, torch.float16):
-        raise TypeError(f'lsq_linear_act_quant_half: x must be a bfloat16 or float16 tensor, got {x.dtype}')
+    _check_half('lsq_linear_act_quant_half', 'x', x)
     fp32 = {'scales': scales} if forced is None else {'scales': scales, 'forced': forced}
-    for dtype, named in ((torch.float32, fp32), (torch.int64, {'planes': planes})):
-        wrong = [name for name, t in named.items() if t.dtype != dtype]
-        if wrong:
-            raise TypeError(f'lsq_linear_act_quant_half: {", ".join(wrong)} must be {dtype} tensors')
-    tensors = [x, planes, *fp32.values()]
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError('lsq_linear_act_quant_half: operands must be contiguous')
-    if x.dim() != 2 or x.numel() == 0 or k < 1:
-        raise ValueError(f'lsq_linear_act_quant_half: bad sizes k={k} for x of shape {tuple(x.shape)}')
-    N, L = x.shape
-    if planes.numel() < k * N * ((L + 63) // 64) or any(tuple(t.shape) != (k, N) for t in fp32.values()):
-        raise ValueError('lsq_linear_act_quant_half: activation planes / scales and (k, N, L) do not match')
-    if scheme in (SCHEME_LS2, SCHEME_LST) and forced is None:
-        raise ValueError('lsq_linear_act_quant_half: ls-2 / ls-T need forced scales (their solve reads fp32 rows: lsq_act_quant)')
-    dev = x.device
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError('lsq_linear_act_quant_half: every operand on the same cuda device')
+
+    def problem():
+        if x.dim() != 2 or x.numel() == 0 or k < 1:
+            return f'bad sizes k={k} for x of shape {tuple(x.shape)}'
+        N, L = x.shape
+        if planes.numel() < k * N * ((L + 63) // 64) or any(tuple(t.shape) != (k, N) for t in fp32.values()):
+            return 'activation planes / scales and (k, N, L) do not match'
+        if scheme in (SCHEME_LS2, SCHEME_LST) and forced is None:
+            return 'ls-2 / ls-T need forced scales (their solve reads fp32 rows: lsq_act_quant)'
+
+    _check_operands('lsq_linear_act_quant_half', fp32, {'planes': planes}, half=[x], problem=problem)
+    (N, L), dev = x.shape, x.device
     passes = 1 if forced is not None else k
     with _on(x), (_Timed('lsq_linear_act_quant_half', N * (2 * L * passes + k * ((L + 63) // 64) * 8), 0)
                   if _timing is not None else _UNTIMED):
@@ -1055,36 +861,7 @@ def linear_act_quant_half(x: torch.Tensor, scheme: int, k: int, alpha: float, pl
             scales.data_ptr(), stream_ptr(dev)), 'lsq_linear_act_quant_half')
 
 
-# ---- the 16-bit free-running ls-2 / ls-T quantizer library (include/lsq_hip_linear_act_solve.h): a ninth shared object,
-# loaded on first use
-_LINEAR_ACT_SOLVE_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_linear_act_solve.so')
-LINEAR_ACT_SOLVE_ABI_VERSION = 1
-_linear_act_solve_lib = None
-
-
-def linear_act_solve_library_path() -> str:
-    return _LINEAR_ACT_SOLVE_LIB_PATH
-
-
-def _declare_linear_act_solve(handle):
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    handle.lsq_linear_act_solve_abi_version.restype = i32
-    handle.lsq_linear_act_solve_abi_version.argtypes = []
-    handle.lsq_linear_act_quant_solve_half.restype = i32
-    handle.lsq_linear_act_quant_solve_half.argtypes = [vp, i32, i64, i64, i32, i32, f32, vp, vp, vp, vp]
-
-
-def linear_act_solve_lib():
-    """Load (once) and return the 16-bit free-running ls-2 / ls-T quantizer library; raises if it has not been built (no
-    fallback, as ``lib()``)."""
-    global _linear_act_solve_lib
-    if _linear_act_solve_lib is None:
-        _linear_act_solve_lib = _load(_LINEAR_ACT_SOLVE_LIB_PATH, 'csrc/linear_act_solve', _declare_linear_act_solve,
-                                      'lsq_linear_act_solve_abi_version', LINEAR_ACT_SOLVE_ABI_VERSION,
-                                      'liblsq_hip_linear_act_solve.so')
-    return _linear_act_solve_lib
-
-
+# ---- the 16-bit free-running ls-2 / ls-T quantizer library (include/lsq_hip_linear_act_solve.h)
 def linear_act_quant_solve_half(x: torch.Tensor, scheme: int, skip: int, alpha: float, planes: torch.Tensor,
                                 scales: torch.Tensor, status: Optional[torch.Tensor] = None) -> None:
     """Free-running ls-2 / ls-T on the bf16 / fp16 rows ``x`` [N, L] (any 2-byte-aligned data pointer): the optimal v1 of the
@@ -1094,63 +871,29 @@ def linear_act_quant_solve_half(x: torch.Tensor, scheme: int, skip: int, alpha: 
     ROUNDED into x's type (as Tensor.clamp rounds it), negative for none."""
     scheme, skip = int(scheme), int(skip)
     what = 'lsq_linear_act_quant_solve_half'
-    if x.dtype not in (torch.bfloat16, torch.float16):
+    if x.dtype not in (torch.bfloat16, torch.float16):        # (a ValueError, unlike _check_half's)
         raise ValueError(f'{what}: x must be a bfloat16 or float16 tensor, got {x.dtype}')
     if scheme not in (SCHEME_LS2, SCHEME_LST):
         raise ValueError(f'{what}: the scheme must be ls-2 or ls-T, got {scheme}')
-    named = ((torch.float32, {'scales': scales}), (torch.int64, {'planes': planes}),
-             (torch.int32, {} if status is None else {'status': status}))
-    for dtype, group in named:
-        wrong = [name for name, t in group.items() if t.dtype != dtype]
-        if wrong:
-            raise TypeError(f'{what}: {", ".join(wrong)} must be {dtype} tensors')
-    tensors = [x, planes, scales] + ([] if status is None else [status])
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError(f'{what}: operands must be contiguous')
-    if x.dim() != 2 or x.numel() == 0 or skip < 1:
-        raise ValueError(f'{what}: bad sizes skip={skip} for x of shape {tuple(x.shape)}')
-    N, L = x.shape
-    if (planes.numel() < 2 * N * ((L + 63) // 64) or tuple(scales.shape) != (2, N)
-            or (status is not None and tuple(status.shape) != (N,))):
-        raise ValueError(f'{what}: activation planes / scales / status and (N, L) do not match')
-    dev = x.device
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError(f'{what}: every operand on the same cuda device')
+
+    def problem():
+        if x.dim() != 2 or x.numel() == 0 or skip < 1:
+            return f'bad sizes skip={skip} for x of shape {tuple(x.shape)}'
+        N, L = x.shape
+        if (planes.numel() < 2 * N * ((L + 63) // 64) or tuple(scales.shape) != (2, N)
+                or (status is not None and tuple(status.shape) != (N,))):
+            return 'activation planes / scales / status and (N, L) do not match'
+
+    _check_operands(what, {'scales': scales}, {'planes': planes}, {} if status is None else {'status': status}, half=[x],
+                    problem=problem)
+    (N, L), dev = x.shape, x.device
     with _on(x), (_Timed(what, N * (2 * L * 2 + 2 * ((L + 63) // 64) * 8), 0) if _timing is not None else _UNTIMED):
         check(linear_act_solve_lib().lsq_linear_act_quant_solve_half(
             x.data_ptr(), LINEAR_HALF_DTYPES[x.dtype], N, L, scheme, skip, float(alpha), planes.data_ptr(), scales.data_ptr(),
             ptr(status), stream_ptr(dev)), what)
 
 
-# ---- the 16-bit activation quantizer of QuantConv2d (include/lsq_hip_conv_act_half.h): a tenth shared object, loaded on
-# first use
-_CONV_ACT_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_conv_act_half.so')
-CONV_ACT_HALF_ABI_VERSION = 1
-_conv_act_half_lib = None
-
-
-def conv_act_half_library_path() -> str:
-    return _CONV_ACT_HALF_LIB_PATH
-
-
-def _declare_conv_act_half(handle):
-    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    handle.lsq_conv_act_half_abi_version.restype = i32
-    handle.lsq_conv_act_half_abi_version.argtypes = []
-    handle.lsq_act_quant_half.restype = i32
-    handle.lsq_act_quant_half.argtypes = [vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
-
-
-def conv_act_half_lib():
-    """Load (once) and return the 16-bit convolution activation quantizer library; raises if it has not been built (no
-    fallback, as ``lib()``)."""
-    global _conv_act_half_lib
-    if _conv_act_half_lib is None:
-        _conv_act_half_lib = _load(_CONV_ACT_HALF_LIB_PATH, 'csrc/conv_act_half', _declare_conv_act_half,
-                                   'lsq_conv_act_half_abi_version', CONV_ACT_HALF_ABI_VERSION, 'liblsq_hip_conv_act_half.so')
-    return _conv_act_half_lib
-
-
+# ---- the 16-bit activation quantizer of QuantConv2d (include/lsq_hip_conv_act_half.h)
 def act_quant_half(x: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: int, alpha: float, planes: torch.Tensor,
                    scales: torch.Tensor, forced: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> None:
     """Sign planes and scales of the bf16 / fp16 batch ``x`` [N, C, H, W] (contiguous, any 2-byte-aligned data pointer) of
@@ -1161,30 +904,22 @@ def act_quant_half(x: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: i
     the free-running ls-2 / ls-T solve."""
     scheme, k, skip = int(scheme), int(k), int(skip)
     what = 'lsq_act_quant_half'
-    if x.dtype not in (torch.bfloat16, torch.float16):
-        raise TypeError(f'{what}: x must be a bfloat16 or float16 tensor, got {x.dtype}')
+    _check_half(what, 'x', x)
     fp32 = {'scales': scales} if forced is None else {'scales': scales, 'forced': forced}
-    named = ((torch.float32, fp32), (torch.int64, {'planes': planes}), (torch.int32, {} if status is None else {'status': status}))
-    for dtype, group in named:
-        wrong = [name for name, t in group.items() if t.dtype != dtype]
-        if wrong:
-            raise TypeError(f'{what}: {", ".join(wrong)} must be {dtype} tensors')
-    tensors = [x, planes, *fp32.values()] + ([] if status is None else [status])
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError(f'{what}: operands must be contiguous')
-    if x.dim() != 4 or x.numel() == 0 or k < 1 or skip < 1:
-        raise ValueError(f'{what}: bad sizes k={k}, skip={skip} for x of shape {tuple(x.shape)}')
-    N, C, H, W = x.shape
-    if (geom.N, geom.C, geom.H, geom.W) != (N, C, H, W) or geom.groups < 1 or C % geom.groups or min(geom.pad_h, geom.pad_w) < 0:
-        raise ValueError(f'{what}: the geometry and x of shape {tuple(x.shape)} do not match')
-    cg = C // geom.groups
-    words = N * geom.groups * ((cg + 63) // 64) * (H + 2 * geom.pad_h) * (W + 2 * geom.pad_w)
-    if (planes.numel() < k * words or any(tuple(t.shape) != (k, N) for t in fp32.values())
-            or (status is not None and tuple(status.shape) != (N,))):
-        raise ValueError(f'{what}: activation planes / scales / status and (k, geometry) do not match')
-    dev = x.device
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError(f'{what}: every operand on the same cuda device')
+
+    def problem():
+        if x.dim() != 4 or x.numel() == 0 or k < 1 or skip < 1:
+            return f'bad sizes k={k}, skip={skip} for x of shape {tuple(x.shape)}'
+        N, C, H, W = x.shape
+        if (geom.N, geom.C, geom.H, geom.W) != (N, C, H, W) or geom.groups < 1 or C % geom.groups or min(geom.pad_h, geom.pad_w) < 0:
+            return f'the geometry and x of shape {tuple(x.shape)} do not match'
+        words = N * geom.groups * ((C // geom.groups + 63) // 64) * (H + 2 * geom.pad_h) * (W + 2 * geom.pad_w)
+        if (planes.numel() < k * words or any(tuple(t.shape) != (k, N) for t in fp32.values())
+                or (status is not None and tuple(status.shape) != (N,))):
+            return 'activation planes / scales / status and (k, geometry) do not match'
+
+    _check_operands(what, fp32, {'planes': planes}, {} if status is None else {'status': status}, half=[x], problem=problem)
+    (N, C, H, W), dev = x.shape, x.device
     m = C * H * W
     passes = 1 if forced is not None and k <= 2 else (2 if scheme in (SCHEME_LS2, SCHEME_LST) and forced is None else k)
     with _on(x), (_Timed(what, N * (2 * m * passes + k * m // 8), 0, f'C{C}_H{H}') if _timing is not None else _UNTIMED):
@@ -1193,46 +928,11 @@ def act_quant_half(x: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: i
             planes.data_ptr(), scales.data_ptr(), ptr(status), stream_ptr(dev)), what)
 
 
-# ---- the 16-bit-activation x sign-weight convolution (include/lsq_hip_conv_half.h): an eleventh shared object, loaded on
-# first use
-_CONV_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_conv_half.so')
-CONV_HALF_ABI_VERSION = 1
-_conv_half_lib = None
-
-
-def conv_half_library_path() -> str:
-    return _CONV_HALF_LIB_PATH
-
-
-def _declare_conv_half(handle):
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    handle.lsq_conv_half_abi_version.restype = i32
-    handle.lsq_conv_half_abi_version.argtypes = []
-    handle.lsq_signw_conv2d_half_plan.restype = i32
-    handle.lsq_signw_conv2d_half_plan.argtypes = [vp]
-    handle.lsq_signw_conv2d_half_workspace_bytes.restype = i64
-    handle.lsq_signw_conv2d_half_workspace_bytes.argtypes = [vp, i32, i32]
-    handle.lsq_signw_conv2d_half.restype = i32
-    handle.lsq_signw_conv2d_half.argtypes = [vp, i32, f32, vp, i32, vp, vp, vp, vp, i32, vp, ctypes.c_size_t, vp]
-
-
-def conv_half_lib():
-    """Load (once) and return the 16-bit-activation convolution library; raises if it has not been built (no fallback, as
-    ``lib()``)."""
-    global _conv_half_lib
-    if _conv_half_lib is None:
-        _conv_half_lib = _load(_CONV_HALF_LIB_PATH, 'csrc/conv_half', _declare_conv_half, 'lsq_conv_half_abi_version',
-                               CONV_HALF_ABI_VERSION, 'liblsq_hip_conv_half.so')
-    return _conv_half_lib
-
-
+# ---- the 16-bit-activation x sign-weight convolution (include/lsq_hip_conv_half.h)
 def signw_conv2d_half_supported(geom: ConvGeom) -> bool:
     """Whether lsq_signw_conv2d_half computes ``geom`` (lsq_signw_conv2d_half_plan, host code: no device call): False for a
     geometry past the library's 32-bit index limits or with an empty output."""
     return conv_half_lib().lsq_signw_conv2d_half_plan(ctypes.byref(geom)) >= 0
-
-
-_conv_half_ws_cache = {}
 
 
 def signw_conv2d_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: torch.Tensor, bias: Optional[torch.Tensor],
@@ -1246,85 +946,42 @@ def signw_conv2d_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscale
     run in order)."""
     what = 'lsq_signw_conv2d_half'
     out_dtype = x.dtype if out_dtype is None else out_dtype
-    if x.dtype not in (torch.bfloat16, torch.float16):
-        raise TypeError(f'{what}: x must be a bfloat16 or float16 tensor, got {x.dtype}')
+    _check_half(what, 'x', x)
     if out_dtype not in (torch.float32, x.dtype):
         raise TypeError(f'{what}: out_dtype must be torch.float32 or {x.dtype}, got {out_dtype}')
-    fp32 = {'wscales': wscales} if bias is None else {'wscales': wscales, 'bias': bias}
-    wrong = [name for name, t in fp32.items() if t.dtype != torch.float32]
-    if wrong:
-        raise TypeError(f'{what}: {", ".join(wrong)} must be torch.float32 tensors')
+    fp32 = _check_dtypes(what, {'wscales': wscales} if bias is None else {'wscales': wscales, 'bias': bias})
     if wbits.dtype != torch.int64:
         raise TypeError(f'{what}: wbits must be a torch.int64 tensor')
-    tensors = [x, wbits, *fp32.values()]
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError(f'{what}: operands must be contiguous')
-    if x.dim() != 4 or x.numel() == 0 or wscales.dim() != 2 or wscales.shape[0] < 1:
-        raise ValueError(f'{what}: bad sizes: x of shape {tuple(x.shape)}, wscales of shape {tuple(wscales.shape)}')
-    N, C, H, W = x.shape
-    if ((geom.N, geom.C, geom.H, geom.W) != (N, C, H, W) or min(geom.O, geom.KH, geom.KW, geom.groups) < 1
-            or C % geom.groups or geom.O % geom.groups):
-        raise ValueError(f'{what}: the geometry and x of shape {tuple(x.shape)} do not match')
-    kw, O = wscales.shape[0], geom.O
-    words = geom.KH * geom.KW * ((C // geom.groups + 63) // 64) * geom.groups * ((O // geom.groups + 15) // 16 * 16)
-    if wscales.shape[1] != O or wbits.numel() < kw * words or (bias is not None and tuple(bias.shape) != (O,)):
-        raise ValueError(f'{what}: weight planes / scales / bias and (kw, geometry) do not match')
-    dev = x.device
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError(f'{what}: every operand on the same cuda device')
+
+    def problem():
+        if x.dim() != 4 or x.numel() == 0 or wscales.dim() != 2 or wscales.shape[0] < 1:
+            return f'bad sizes: x of shape {tuple(x.shape)}, wscales of shape {tuple(wscales.shape)}'
+        if (geom.N, geom.C, geom.H, geom.W) != tuple(x.shape) or min(geom.O, geom.KH, geom.KW, geom.groups) < 1 \
+                or geom.C % geom.groups or geom.O % geom.groups:
+            return f'the geometry and x of shape {tuple(x.shape)} do not match'
+        if wscales.shape[1] != geom.O or wbits.numel() < wscales.shape[0] * _signw_plane_words(geom) \
+                or (bias is not None and tuple(bias.shape) != (geom.O,)):
+            return 'weight planes / scales / bias and (kw, geometry) do not match'
+
+    _check_placement(what, [x, wbits, *fp32], problem)
+    (N, C, H, W), kw, O, dev = x.shape, wscales.shape[0], geom.O, x.device
     ho, wo = out_hw(geom)
     if ho < 1 or wo < 1:
         raise ValueError(f'{what}: the geometry has an empty output')
     hl = conv_half_lib()
     xdt, ydt = LINEAR_HALF_DTYPES[x.dtype], LINEAR_HALF_DTYPES[out_dtype]
     need = int(hl.lsq_signw_conv2d_half_workspace_bytes(ctypes.byref(geom), kw, ydt))
-    ws = _stream_buffer(_conv_half_ws_cache, need, dev) if need else None
+    ws = _stream_buffer('conv_half', need, dev) if need else None
     y = torch.empty((N, O, ho, wo), dtype=out_dtype, device=dev)
     nbytes = 2 * x.numel() + 8 * y.numel() * (kw - 1) + y.element_size() * y.numel()    # (the fp32 sum is read back per plane)
     with _on(y), (_Timed(what, nbytes, 2 * y.numel() * (C // geom.groups) * geom.KH * geom.KW * kw,
                          f'C{C}_H{H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
         check(hl.lsq_signw_conv2d_half(x.data_ptr(), xdt, float(alpha), wbits.data_ptr(), kw, wscales.data_ptr(), ptr(bias),
-                                       ctypes.byref(geom), y.data_ptr(), ydt, ptr(ws), 0 if ws is None else ws.numel(),
-                                       stream_ptr(dev)), what)
+                                       ctypes.byref(geom), y.data_ptr(), ydt, *_ws_args(ws), stream_ptr(dev)), what)
     return y
 
 
-# ---- the convolution layer's training library (include/lsq_hip_conv_train.h): a twelfth shared object, loaded on first use
-_CONV_TRAIN_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_conv_train.so')
-CONV_TRAIN_ABI_VERSION = 1
-_conv_train_lib = None
-
-
-class ConvDgradPlan(ctypes.Structure):
-    _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'classes', 'dead_classes', 'tap_steps')]
-
-
-def conv_train_library_path() -> str:
-    return _CONV_TRAIN_LIB_PATH
-
-
-def _declare_conv_train(handle):
-    vp, i32 = ctypes.c_void_p, ctypes.c_int
-    handle.lsq_conv_train_abi_version.restype = i32
-    handle.lsq_conv_train_abi_version.argtypes = []
-    handle.lsq_signw_conv2d_dgrad_plan.restype = i32
-    handle.lsq_signw_conv2d_dgrad_plan.argtypes = [vp, vp]
-    handle.lsq_signw_conv2d_dgrad_workspace_bytes.restype = ctypes.c_size_t
-    handle.lsq_signw_conv2d_dgrad_workspace_bytes.argtypes = [vp, i32]
-    handle.lsq_signw_conv2d_dgrad.restype = i32
-    handle.lsq_signw_conv2d_dgrad.argtypes = [vp, vp, i32, vp, vp, vp, vp, ctypes.c_size_t, vp]
-
-
-def conv_train_lib():
-    """Load (once) and return the convolution layer's training library; raises if it has not been built (no fallback, as
-    ``lib()``)."""
-    global _conv_train_lib
-    if _conv_train_lib is None:
-        _conv_train_lib = _load(_CONV_TRAIN_LIB_PATH, 'csrc/conv_train', _declare_conv_train, 'lsq_conv_train_abi_version',
-                                CONV_TRAIN_ABI_VERSION, 'liblsq_hip_conv_train.so')
-    return _conv_train_lib
-
-
+# ---- the convolution layer's training library (include/lsq_hip_conv_train.h)
 def signw_conv2d_dgrad_plan(geom: ConvGeom) -> Optional[ConvDgradPlan]:
     """The plan of lsq_signw_conv2d_dgrad for the forward geometry ``geom`` (host code: no device call), None where the
     call would refuse it."""
@@ -1338,83 +995,39 @@ def signw_conv2d_dgrad_supported(geom: ConvGeom) -> bool:
     return signw_conv2d_dgrad_plan(geom) is not None
 
 
-_conv_dgrad_ws_cache = {}
-
-
 def signw_conv2d_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Tensor, geom: ConvGeom) -> torch.Tensor:
     """grad_xq [N, C, H, W] = conv2d_input(w_q, gy) for the fp32 output gradient ``gy`` [N, O, Ho, Wo] of the FORWARD geometry
     ``geom`` and the sign planes ``wbits`` / scales ``wscales`` [kw, O] lsq_pack_weight took and wrote for ``geom`` -- the
     forward's own operands (lsq_signw_conv2d_dgrad).  The transposed plane image lives in a workspace cached per
     (device, stream) like the solver's (rewritten by every call; kernels of one stream run in order)."""
     what = 'lsq_signw_conv2d_dgrad'
-    wrong = [name for name, t in (('gy', gy), ('wscales', wscales)) if t.dtype != torch.float32]
-    if wrong:
-        raise TypeError(f'{what}: {", ".join(wrong)} must be torch.float32 tensors')
+    _check_dtypes(what, {'gy': gy, 'wscales': wscales})
     if wbits.dtype != torch.int64:
         raise TypeError(f'{what}: wbits must be a torch.int64 tensor')
-    tensors = [gy, wbits, wscales]
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError(f'{what}: operands must be contiguous')
-    if gy.dim() != 4 or gy.numel() == 0 or wscales.dim() != 2 or not 1 <= wscales.shape[0] <= MAX_PLANES:
-        raise ValueError(f'{what}: bad sizes: gy of shape {tuple(gy.shape)}, wscales of shape {tuple(wscales.shape)}')
-    if (min(geom.N, geom.C, geom.H, geom.W, geom.O, geom.KH, geom.KW, geom.groups, geom.stride_h, geom.stride_w,
-            geom.dil_h, geom.dil_w) < 1 or min(geom.pad_h, geom.pad_w) < 0 or geom.C % geom.groups or geom.O % geom.groups
-            or tuple(gy.shape) != (geom.N, geom.O) + tuple(out_hw(geom))):
-        raise ValueError(f'{what}: the geometry and gy of shape {tuple(gy.shape)} do not match')
-    kw, O, C = wscales.shape[0], geom.O, geom.C
-    words = geom.KH * geom.KW * ((C // geom.groups + 63) // 64) * geom.groups * ((O // geom.groups + 15) // 16 * 16)
-    if wscales.shape[1] != O or wbits.numel() != kw * words:
-        raise ValueError(f'{what}: weight planes / scales and (kw, geometry) do not match')
-    dev = gy.device
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError(f'{what}: every operand on the same cuda device')
+
+    def problem():
+        if gy.dim() != 4 or gy.numel() == 0 or wscales.dim() != 2 or not 1 <= wscales.shape[0] <= MAX_PLANES:
+            return f'bad sizes: gy of shape {tuple(gy.shape)}, wscales of shape {tuple(wscales.shape)}'
+        if not _geom_matches_gy(geom, gy):
+            return f'the geometry and gy of shape {tuple(gy.shape)} do not match'
+        if wscales.shape[1] != geom.O or wbits.numel() != wscales.shape[0] * _signw_plane_words(geom):
+            return 'weight planes / scales and (kw, geometry) do not match'
+
+    _check_placement(what, [gy, wbits, wscales], problem)
+    kw, C, words, dev = wscales.shape[0], geom.C, _signw_plane_words(geom), gy.device
     tl = conv_train_lib()
     need = int(tl.lsq_signw_conv2d_dgrad_workspace_bytes(ctypes.byref(geom), kw))
-    ws = _stream_buffer(_conv_dgrad_ws_cache, need, dev) if need else None
+    ws = _stream_buffer('conv_dgrad', need, dev) if need else None
     gx = torch.empty((geom.N, C, geom.H, geom.W), dtype=torch.float32, device=dev)
     with _on(gx), (_Timed(what, 4 * gy.numel() + 8 * kw * words + 2 * need + 4 * gx.numel(),
                           2 * 2 * gy.numel() * (C // geom.groups) * geom.KH * geom.KW * kw,       # (hi and lo pass)
                           f'C{C}_H{geom.H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
         check(tl.lsq_signw_conv2d_dgrad(gy.data_ptr(), wbits.data_ptr(), kw, wscales.data_ptr(), ctypes.byref(geom),
-                                        gx.data_ptr(), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev)), what)
+                                        gx.data_ptr(), *_ws_args(ws), stream_ptr(dev)), what)
     return gx
 
 
-# ---- the convolution layer's 16-bit training library (include/lsq_hip_conv_train_half.h): a thirteenth shared object, loaded
-# on first use
-_CONV_TRAIN_HALF_LIB_PATH = os.path.join(_LIB_DIR, 'liblsq_hip_conv_train_half.so')
-CONV_TRAIN_HALF_ABI_VERSION = 1
-CONV_DGRAD_HALF_MAX_SAMPLES = 65535    # lsq_signw_conv2d_dgrad_half with x: N <= 65535 (the limit of lsq_ste_backward)
-_conv_train_half_lib = None
-
-
-def conv_train_half_library_path() -> str:
-    return _CONV_TRAIN_HALF_LIB_PATH
-
-
-def _declare_conv_train_half(handle):
-    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    handle.lsq_conv_train_half_abi_version.restype = i32
-    handle.lsq_conv_train_half_abi_version.argtypes = []
-    handle.lsq_signw_conv2d_dgrad_half_plan.restype = i32
-    handle.lsq_signw_conv2d_dgrad_half_plan.argtypes = [vp, vp]
-    handle.lsq_signw_conv2d_dgrad_half_workspace_bytes.restype = ctypes.c_size_t
-    handle.lsq_signw_conv2d_dgrad_half_workspace_bytes.argtypes = [vp, i32]
-    handle.lsq_signw_conv2d_dgrad_half.restype = i32
-    handle.lsq_signw_conv2d_dgrad_half.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, ctypes.c_size_t, vp]
-
-
-def conv_train_half_lib():
-    """Load (once) and return the convolution layer's 16-bit training library; raises if it has not been built (no fallback,
-    as ``lib()``)."""
-    global _conv_train_half_lib
-    if _conv_train_half_lib is None:
-        _conv_train_half_lib = _load(_CONV_TRAIN_HALF_LIB_PATH, 'csrc/conv_train_half', _declare_conv_train_half,
-                                     'lsq_conv_train_half_abi_version', CONV_TRAIN_HALF_ABI_VERSION,
-                                     'liblsq_hip_conv_train_half.so')
-    return _conv_train_half_lib
-
-
+# ---- the convolution layer's 16-bit training library (include/lsq_hip_conv_train_half.h)
 def signw_conv2d_dgrad_half_plan(geom: ConvGeom) -> Optional[ConvDgradPlan]:
     """The plan of lsq_signw_conv2d_dgrad_half for the forward geometry ``geom`` (host code: no device call), None where the
     call would refuse it: for every geometry what ``signw_conv2d_dgrad_plan`` returns."""
@@ -1426,9 +1039,6 @@ def signw_conv2d_dgrad_half_supported(geom: ConvGeom) -> bool:
     """Whether lsq_signw_conv2d_dgrad_half computes the forward geometry ``geom``: False past the library's 32-bit index and
     grid limits or with an empty output."""
     return signw_conv2d_dgrad_half_plan(geom) is not None
-
-
-_conv_dgrad_half_ws_cache = {}
 
 
 def signw_conv2d_dgrad_half(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Tensor, geom: ConvGeom,
@@ -1444,48 +1054,39 @@ def signw_conv2d_dgrad_half(gy: torch.Tensor, wbits: torch.Tensor, wscales: torc
     in a workspace cached per (device, stream) like the solver's (rewritten by every call; kernels of one stream run in
     order)."""
     what = 'lsq_signw_conv2d_dgrad_half'
-    if gy.dtype not in (torch.bfloat16, torch.float16):
-        raise TypeError(f'{what}: gy must be a bfloat16 or float16 tensor, got {gy.dtype}')
+    _check_half(what, 'gy', gy)
     out_dtype = gy.dtype if out_dtype is None else out_dtype
     if out_dtype not in (torch.float32, gy.dtype):
         raise TypeError(f'{what}: out_dtype must be torch.float32 or {gy.dtype}, got {out_dtype}')
     if x is not None and x.dtype != gy.dtype:
         raise TypeError(f'{what}: x must be of gy\'s type {gy.dtype}, got {x.dtype}')
-    fp32 = {'wscales': wscales} if xscales is None else {'wscales': wscales, 'xscales': xscales}
-    wrong = [name for name, t in fp32.items() if t.dtype != torch.float32]
-    if wrong:
-        raise TypeError(f'{what}: {", ".join(wrong)} must be torch.float32 tensors')
+    fp32 = _check_dtypes(what, {'wscales': wscales} if xscales is None else {'wscales': wscales, 'xscales': xscales})
     if wbits.dtype != torch.int64:
         raise TypeError(f'{what}: wbits must be a torch.int64 tensor')
     if xscales is not None and x is None:
         raise ValueError(f'{what}: xscales without x')
-    tensors = [gy, wbits, *fp32.values()] + ([] if x is None else [x])
-    if any(not t.is_contiguous() for t in tensors):
-        raise ValueError(f'{what}: operands must be contiguous')
-    if gy.dim() != 4 or gy.numel() == 0 or wscales.dim() != 2 or not 1 <= wscales.shape[0] <= MAX_PLANES:
-        raise ValueError(f'{what}: bad sizes: gy of shape {tuple(gy.shape)}, wscales of shape {tuple(wscales.shape)}')
-    if xscales is not None and (xscales.dim() != 2 or not 1 <= xscales.shape[0] <= MAX_PLANES):
-        raise ValueError(f'{what}: bad sizes: xscales of shape {tuple(xscales.shape)}')
-    if (min(geom.N, geom.C, geom.H, geom.W, geom.O, geom.KH, geom.KW, geom.groups, geom.stride_h, geom.stride_w,
-            geom.dil_h, geom.dil_w) < 1 or min(geom.pad_h, geom.pad_w) < 0 or geom.C % geom.groups or geom.O % geom.groups
-            or tuple(gy.shape) != (geom.N, geom.O) + tuple(out_hw(geom))):
-        raise ValueError(f'{what}: the geometry and gy of shape {tuple(gy.shape)} do not match')
-    kw, O, C = wscales.shape[0], geom.O, geom.C
-    words = geom.KH * geom.KW * ((C // geom.groups + 63) // 64) * geom.groups * ((O // geom.groups + 15) // 16 * 16)
-    if wscales.shape[1] != O or wbits.numel() != kw * words:
-        raise ValueError(f'{what}: weight planes / scales and (kw, geometry) do not match')
-    if x is not None and tuple(x.shape) != (geom.N, C, geom.H, geom.W):
-        raise ValueError(f'{what}: the geometry and x of shape {tuple(x.shape)} do not match')
-    if xscales is not None and xscales.shape[1] != geom.N:
-        raise ValueError(f'{what}: activation scales and (kx, geometry) do not match')
-    if x is not None and geom.N > CONV_DGRAD_HALF_MAX_SAMPLES:
-        raise ValueError(f'{what}: at most {CONV_DGRAD_HALF_MAX_SAMPLES} samples with x, got {geom.N}')
-    dev = gy.device
-    if dev.type != 'cuda' or any(t.device != dev for t in tensors):
-        raise ValueError(f'{what}: every operand on the same cuda device')
+
+    def problem():
+        if gy.dim() != 4 or gy.numel() == 0 or wscales.dim() != 2 or not 1 <= wscales.shape[0] <= MAX_PLANES:
+            return f'bad sizes: gy of shape {tuple(gy.shape)}, wscales of shape {tuple(wscales.shape)}'
+        if xscales is not None and (xscales.dim() != 2 or not 1 <= xscales.shape[0] <= MAX_PLANES):
+            return f'bad sizes: xscales of shape {tuple(xscales.shape)}'
+        if not _geom_matches_gy(geom, gy):
+            return f'the geometry and gy of shape {tuple(gy.shape)} do not match'
+        if wscales.shape[1] != geom.O or wbits.numel() != wscales.shape[0] * _signw_plane_words(geom):
+            return 'weight planes / scales and (kw, geometry) do not match'
+        if x is not None and tuple(x.shape) != (geom.N, geom.C, geom.H, geom.W):
+            return f'the geometry and x of shape {tuple(x.shape)} do not match'
+        if xscales is not None and xscales.shape[1] != geom.N:
+            return 'activation scales and (kx, geometry) do not match'
+        if x is not None and geom.N > CONV_DGRAD_HALF_MAX_SAMPLES:
+            return f'at most {CONV_DGRAD_HALF_MAX_SAMPLES} samples with x, got {geom.N}'
+
+    _check_placement(what, [gy, wbits, *fp32] + ([] if x is None else [x]), problem)
+    kw, C, words, dev = wscales.shape[0], geom.C, _signw_plane_words(geom), gy.device
     tl = conv_train_half_lib()
     need = int(tl.lsq_signw_conv2d_dgrad_half_workspace_bytes(ctypes.byref(geom), kw))
-    ws = _stream_buffer(_conv_dgrad_half_ws_cache, need, dev) if need else None
+    ws = _stream_buffer('conv_dgrad_half', need, dev) if need else None
     gx = torch.empty((geom.N, C, geom.H, geom.W), dtype=out_dtype, device=dev)
     kx = 0 if xscales is None else xscales.shape[0]
     nbytes = 2 * gy.numel() + 8 * kw * words + 2 * need + gx.element_size() * gx.numel() + (0 if x is None else 2 * x.numel())
@@ -1493,8 +1094,7 @@ def signw_conv2d_dgrad_half(gy: torch.Tensor, wbits: torch.Tensor, wscales: torc
                           f'C{C}_H{geom.H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
         check(tl.lsq_signw_conv2d_dgrad_half(gy.data_ptr(), LINEAR_HALF_DTYPES[gy.dtype], wbits.data_ptr(), kw,
                                              wscales.data_ptr(), ctypes.byref(geom), ptr(x), kx, ptr(xscales), float(alpha),
-                                             gx.data_ptr(), LINEAR_HALF_DTYPES[out_dtype], ptr(ws),
-                                             0 if ws is None else ws.numel(), stream_ptr(dev)), what)
+                                             gx.data_ptr(), LINEAR_HALF_DTYPES[out_dtype], *_ws_args(ws), stream_ptr(dev)), what)
     return gx
 
 

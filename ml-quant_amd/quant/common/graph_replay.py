@@ -47,7 +47,7 @@ class GraphedForward:
         from quant import _hip
         key = (self.static_input.device.index, self.stream.cuda_stream)
         from quant.binary import chain
-        self._keepalive = [_hip._ws_cache.get(key), _hip._sweep_ws_cache.get(key), chain._arenas.get(key)]
+        self._keepalive = [_hip._ws_caches['solver'].get(key), _hip._ws_caches['sweep'].get(key), chain._arenas.get(key)]
         for m in self.model.modules():
             cache = getattr(m, '_hip_cache', None)
             if isinstance(cache, dict):

@@ -173,8 +173,9 @@ def test_python_wrapper_checks_operands_on_the_host(hip):
 
 
 def test_a_missing_library_is_an_error(hip, monkeypatch, tmp_path):
-    monkeypatch.setattr(hip, '_CONV_TRAIN_LIB_PATH', str(tmp_path / 'liblsq_hip_conv_train.so'))
-    monkeypatch.setattr(hip, '_conv_train_lib', None)
+    monkeypatch.setattr(hip, '_LIB_DIR', str(tmp_path))              # (where the libraries are looked for: none is there)
+    monkeypatch.delitem(hip._handles, 'conv_train', raising=False)
+    assert hip.conv_train_library_path() == str(tmp_path / 'liblsq_hip_conv_train.so')
     with pytest.raises(hip.LsqHipError, match='csrc/conv_train'):
         hip.conv_train_lib()
     with pytest.raises(hip.LsqHipError):

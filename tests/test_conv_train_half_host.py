@@ -98,8 +98,9 @@ def test_library_exports_exactly_the_declared_entry_points(hip):
 
 
 def test_a_missing_library_is_an_error(hip, monkeypatch, tmp_path):
-    monkeypatch.setattr(hip, '_CONV_TRAIN_HALF_LIB_PATH', str(tmp_path / 'liblsq_hip_conv_train_half.so'))
-    monkeypatch.setattr(hip, '_conv_train_half_lib', None)
+    monkeypatch.setattr(hip, '_LIB_DIR', str(tmp_path))              # (where the libraries are looked for: none is there)
+    monkeypatch.delitem(hip._handles, 'conv_train_half', raising=False)
+    assert hip.conv_train_half_library_path() == str(tmp_path / 'liblsq_hip_conv_train_half.so')
     with pytest.raises(hip.LsqHipError, match='csrc/conv_train_half'):
         hip.conv_train_half_lib()
     with pytest.raises(hip.LsqHipError):

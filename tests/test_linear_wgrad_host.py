@@ -125,8 +125,9 @@ def test_python_wrapper_checks_operands_on_the_host(hip):
 
 
 def test_a_missing_library_is_an_error(hip, monkeypatch, tmp_path):
-    monkeypatch.setattr(hip, '_LINEAR_WGRAD_LIB_PATH', str(tmp_path / 'liblsq_hip_linear_wgrad.so'))
-    monkeypatch.setattr(hip, '_linear_wgrad_lib', None)
+    monkeypatch.setattr(hip, '_LIB_DIR', str(tmp_path))              # (where the libraries are looked for: none is there)
+    monkeypatch.delitem(hip._handles, 'linear_wgrad', raising=False)
+    assert hip.linear_wgrad_library_path() == str(tmp_path / 'liblsq_hip_linear_wgrad.so')
     with pytest.raises(hip.LsqHipError, match='csrc/linear_wgrad'):
         hip.linear_wgrad_lib()
 
