@@ -40,7 +40,18 @@ struct ConvArgs {
   double nq_magic, nq_inv_unit;        // 1.5 * 2^(52 + e) and 2^-e
   int nq_Hp, nq_Wp, nq_ph, nq_pw;
   int tap_xoff[64];                    // (kh*dil_h)*Wp + kw*dil_w per tap
+  // ---- projection shortcut computed in the epilogue's residual registers (lsq_xnor_conv2d_proj; the PROJ instantiations of
+  // lsq_xnor_mfma.hip only): residual[n, o, ho, wo] = sum_c proj_w[o, c] * proj_x[n, c, ho * s, wo * s] + proj_bias[o]
+  const float* proj_x;                 // [N][proj_c][proj_h][proj_w_in] fp32 or null (no projection)
+  const float* proj_w;                 // [O][proj_c]
+  const float* proj_bias;              // [O] or null
+  int proj_c, proj_h, proj_w_in, proj_stride;
+  int proj_post;                       // 0: the value plays res_pre, 1: res_post
 };
+
+// The projection operand of lsq_xnor_conv2d_proj's kernel: channels a multiple of 64 (the k order of lsq_pointwise.hip, in
+// chunks of 64), at most kProjMaxChannels (32 x (C + 4) floats of LDS next to the weight fragments).
+constexpr int kProjMaxChannels = 512;
 
 // A block's tensors go from kernel to kernel through the 256 MiB Infinity Cache.  Where a launch reads a tensor for the last time
 // while it writes one of the same size and the two do not fit together (the 56 x 56 layers at batch 256: 205 MB each), the dead
@@ -53,6 +64,8 @@ constexpr int kXnorMfmaNotEligible = 1;
 // One launch (one weight plane x kx <= 2 activation planes) on the matrix cores; kXnorMfmaNotEligible when the
 // geometry is not covered (the caller then takes the popcount kernel), else hipGetLastError().
 int xnor_conv_mfma(const ConvArgs& a, int kx, int groups, hipStream_t st);
+// Whether xnor_conv_mfma takes the geometry (no launch): what lsq_xnor_conv2d_proj must know before it launches anything.
+bool xnor_conv_mfma_eligible(const ConvArgs& a, int kx, int groups);
 
 }  // namespace lsq
 #endif  // LSQ_XNOR_CONV_H_

@@ -20,6 +20,7 @@
 #include <atomic>
 
 #include "lsq_xnor_conv.h"
+#include "lsq_hip_conv_proj.h"
 
 #include <cstdlib>
 
@@ -257,7 +258,9 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
                             const int32_t* wsum, int kw_planes, const float* wscales, const float* bias,
                             const lsq_conv_geom* g, int relu, const float* act_slope, const float* res_pre,
                             const float* res_post, float* y, void* stream,
-                            const int64_t* x_units, float x_alpha, const lsq_next_ls1* next) {
+                            const int64_t* x_units, float x_alpha, const lsq_next_ls1* next, const lsq_proj* proj = nullptr,
+                            bool with_proj = false) {
+  if (with_proj && (!proj || !proj->x || !proj->w)) return LSQ_E_NULL;
   if (!xplanes || (!xscales && !x_units) || !wbits || !wsum || !wscales || !y) return LSQ_E_NULL;
   if (int e = check_geom(g)) return e;
   if (kx < 1 || kx > LSQ_MAX_PLANES || kw_planes < 1 || kw_planes > LSQ_MAX_PLANES) return LSQ_E_SCHEME;
@@ -320,6 +323,23 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
       if ((long long)g->N * (g->O / 64) * a.nq_Hp * a.nq_Wp >= (1ll << 30)) return LSQ_E_UNSUPPORTED;
     }
   }
+  if (with_proj) {
+    // the projection computed in the residual registers (the PROJ kernels of lsq_xnor_mfma.hip): every refusal here, before
+    // any launch; LSQ_E_UNSUPPORTED sends the caller to lsq_pointwise_conv + lsq_xnor_conv2d
+    if (proj->C <= 0 || proj->H <= 0 || proj->W <= 0 || proj->stride <= 0) return LSQ_E_SHAPE;
+    if ((proj->H - 1) / proj->stride + 1 != Ho || (proj->W - 1) / proj->stride + 1 != Wo) return LSQ_E_SHAPE;
+    if (proj->post ? res_post != nullptr : res_pre != nullptr) return LSQ_E_SCHEME;
+    if (proj->C % 64 || proj->C > kProjMaxChannels || (long long)g->N * proj->C * proj->H * proj->W >= (1ll << 30))
+      return LSQ_E_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(proj->w) & 15) return LSQ_E_UNSUPPORTED;      // (the weights are staged with 16-byte loads)
+    if (kx != 2 || kw_planes != 1 || (proj->post && res_pre) || g_force_popcount.load(std::memory_order_relaxed) != 0)
+      return LSQ_E_UNSUPPORTED;
+    if (!xnor_conv_mfma_eligible(a, 2, g->groups)) return LSQ_E_UNSUPPORTED;
+    a.proj_x = proj->x; a.proj_w = proj->w; a.proj_bias = proj->bias;
+    a.proj_c = proj->C; a.proj_h = proj->H; a.proj_w_in = proj->W; a.proj_stride = proj->stride;
+    a.proj_post = proj->post ? 1 : 0;
+    a.res_stream = 0;              // (no residual tensor is streamed: a res_post tensor beside a res_pre projection is read in place)
+  }
   const long long wplane_words = lsq_weight_plane_words(g);
   const int taps = g->KH * g->KW;
   hipStream_t st = (hipStream_t)stream;
@@ -354,6 +374,17 @@ extern "C" int lsq_xnor_conv2d(const uint64_t* xplanes, int kx, const float* xsc
   return xnor_conv2d_impl(xplanes, kx, xscales, wbits, wsum, kw_planes, wscales, bias, g, relu, act_slope, res_pre, res_post, y,
                           stream, nullptr, -1.f, nullptr);
 }
+
+namespace lsq {
+// lsq_xnor_conv2d_proj of liblsq_hip_conv_proj.so (include/lsq_hip_conv_proj.h), which links this library for it
+int xnor_conv2d_proj(const uint64_t* xplanes, int kx, const float* xscales, const uint64_t* wbits, const int32_t* wsum,
+                     int kw_planes, const float* wscales, const float* bias, const lsq_conv_geom* g, int act,
+                     const float* act_slope, const float* res_pre, const float* res_post, const lsq_proj* proj, float* y,
+                     void* stream) {
+  return xnor_conv2d_impl(xplanes, kx, xscales, wbits, wsum, kw_planes, wscales, bias, g, act, act_slope, res_pre, res_post, y,
+                          stream, nullptr, -1.f, nullptr, proj, true);
+}
+}  // namespace lsq
 
 extern "C" int lsq_xnor_conv2d_chain(const uint64_t* xplanes, const float* xscales, const int64_t* x_units, float x_alpha,
                                      const uint64_t* wbits, const int32_t* wsum, int kw_planes, const float* wscales,

@@ -1,5 +1,7 @@
-// Binary x binary 3x3 convolution on the integer matrix cores of gfx950 (v_mfma_i32_32x32x32_i8) for 64, 128, 256
-// and 512 input channels -- all sixteen quantized layers of ResNet-18.  Second implementation of
+// Binary x binary 3x3 convolution on the matrix cores of gfx950 for 64, 128, 256 and 512 input channels -- all sixteen
+// quantized layers of ResNet-18: fp4 operands on v_mfma_scale_f32_32x32x64_f8f6f4 (FP4, the product path since round 6) or
+// int8 operands on v_mfma_i32_32x32x32_i8 (the kernel of rounds 2-5, kept as the comparator; the comments below describe it
+// first and the fp4 variant where the template is declared).  Second implementation of
 // F.conv2d(x_q, w_q, ...) of quant/binary/binary_conv.py:165-173 next to the popcount kernel (lsq_xnor_conv.hip, every
 // other geometry): same operands, same epilogue arithmetic, bit-identical output (tests/test_gpu_parity.py).
 //
@@ -55,8 +57,18 @@ constexpr unsigned kM0 = 0x01010101u;
 // 4), so every product is +-2 or 0 and the fp32 accumulator, started at the border term fc, IS (b * s): integers below 2^14,
 // exact in any order.  Half the operand-build instructions, half the MFMAs and half the LDS bytes per binary MAC;
 // scripts/ubench/fp4_mfma_check.hip is the known-answer test of the instruction (subnormal code 1 = 0.5 included).
-template <int KX, int GG, int TAPS, int NWAVES, int WPC, bool CHAIN, bool FP4>
+//
+// PROJ (FP4, unchained launches of lsq_xnor_conv2d_proj): the residual operand is not read from memory but COMPUTED per tile,
+// the strided 1x1 projection shortcut of a down-sampling block (lsq_pointwise.hip) on v_mfma_f32_32x32x2_f32 with A = weights,
+// B = x -- that instruction's D[o][pixel] is this kernel's accumulator layout, so its sixteen values per lane land in rv[16].
+// Same k order as pointwise_all_kernel (chunks of 64 channels, lane half g supplies channel 64 cc + 32 g + 16 h + 4 q + e):
+// the same fmaf chain, the same bits.  The workgroup's 32 x Cp weights sit in (dynamic) LDS at a pitch of Cp + 4 floats; a
+// lane gathers its pixel's x with 4-byte loads, chunk c + 1 in flight during the MFMAs of chunk c.
+extern __shared__ __attribute__((aligned(16))) float s_pw[];         // PROJ: [32 out-channels][Cp + 4]
+
+template <int KX, int GG, int TAPS, int NWAVES, int WPC, bool CHAIN, bool FP4, bool PROJ = false>
 __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a) {
+  static_assert(!PROJ || (FP4 && !CHAIN), "the projection runs in the unchained fp4 kernel only");
   constexpr int NT = 64 * NWAVES;
   constexpr int FPS = FP4 ? 1 : 2;               // 16-byte weight fragments per (word, tap) step: int8 K = 32 twice, fp4 K = 64 once
   constexpr int NF = TAPS * GG * FPS;            // 16-byte operand fragments per lane
@@ -69,6 +81,7 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
   __shared__ __attribute__((aligned(16))) short s_fc[8][8][32];    // |.| <= taps * channels = 4608
   __shared__ __attribute__((aligned(16))) float s_scale[32], s_bias[32], s_slope[32];
   __shared__ float s_nqs[CHAIN ? 32 : 1], s_nqt[CHAIN ? 32 : 1];      // chained layers: the next quantizer's folded batch norm
+  __shared__ __attribute__((aligned(16))) float s_pbias[PROJ ? 32 : 1];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int col = lane & 31, hh = lane >> 5;
   const int o0 = blockIdx.y * 32;
@@ -86,7 +99,9 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
   const int d_r = (int)(dstep - (unsigned)d_n * (unsigned)HoWo);
   const int d_ho = d_r / a.Wo, d_wo = d_r - d_ho * a.Wo;
   const bool acc_in = a.accumulate != 0, fin = a.final_pass != 0;
-  const bool want_pre = fin && a.res_pre, want_post = fin && a.res_post;
+  // (PROJ: the projection takes one of the two slots; the entry point admits no tensor in that slot, and none in res_pre
+  //  when the projection plays res_post -- rv[] is the one residual array in registers)
+  const bool want_pre = fin && (a.res_pre || (PROJ && !a.proj_post)), want_post = fin && (a.res_post || (PROJ && a.proj_post));
   const bool relu = fin && a.relu == LSQ_ACT_RELU, prelu = fin && a.relu >= LSQ_ACT_PRELU;
   const int ob = 4 * hh;                         // the lane's out-channel of register i: ob + (i & 3) + 8 (i >> 2)
 
@@ -181,6 +196,19 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
     const int i = min(tid + k * NT, TAPS * 32 - 1);
     wsv[k] = a.wsum[(long long)(o0 + (i & 31)) * TAPS + (i >> 5)];
   }
+  // PROJ: the 32 x Cp projection weights of the out-channel tile as 16-byte loads, 8 Cp of them over the workgroup
+  constexpr int kPIter = PROJ ? (8 * kProjMaxChannels + NT - 1) / NT : 1;
+  const int pitch = a.proj_c + 4, pq = a.proj_c >> 2, pn4 = 32 * pq;      // LDS pitch in floats, float4s per row and in all
+  float4 pwv[kPIter];
+  float c_pb = 0.f;
+  if constexpr (PROJ) {
+#pragma unroll
+    for (int k = 0; k < kPIter; ++k) {
+      const int e = min(tid + k * NT, pn4 - 1);
+      pwv[k] = reinterpret_cast<const float4*>(a.proj_w + (long long)o0 * a.proj_c)[e];      // rows are contiguous: [32][Cp]
+    }
+    if (tid < 32 && a.proj_bias) c_pb = a.proj_bias[o0 + tid];
+  }
   float c_sc = 0.f, c_bi = 0.f, c_sl = 0.f, c_ns = 1.f, c_nt = 0.f;
   if (tid < 32) {
     c_sc = a.wscale[o0 + tid];
@@ -239,6 +267,17 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
       s_nqs[tid] = c_ns;
       s_nqt[tid] = c_nt;
     }
+    if constexpr (PROJ) s_pbias[tid] = c_pb;
+  }
+  if constexpr (PROJ) {
+#pragma unroll
+    for (int k = 0; k < kPIter; ++k) {
+      const int e = tid + k * NT;
+      if (e < pn4) {
+        const int row = e / pq, c4 = e - row * pq;
+        *reinterpret_cast<float4*>(&s_pw[row * pitch + 4 * c4]) = pwv[k];
+      }
+    }
   }
   __syncthreads();
   for (int i = tid; i < 8 * 8 * 32; i += NT) {
@@ -291,7 +330,61 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
     for (int p = 0; p < KX; ++p) xs[p] = (!CHAIN || a.xscales) ? a.xscales[p * a.N + ln] * kAccUnit : 0.f;
     if (CHAIN && a.xunits)          // chained ls-1 layer: the scale is the exact row sum the producer's epilogue left, / M as the sweeps do
       xs[0] = (float)(((double)a.xunits[ln] * a.xunit) / a.xM) * kAccUnit;
-    if (want_pre || want_post) {
+    if constexpr (PROJ) {
+      // The projection tile: sixteen fp32 accumulators from zero, Cp / 2 MFMAs in steps of SZ; the x values of step s + 1 are
+      // requested before the MFMAs of step s (two register sets of SZ).  MFMA m of the k loop multiplies channel
+      // 64 (m >> 5) + 32 hh + (m & 31).  Lanes past the last pixel gather image 0 and store nothing.
+      constexpr int SZ = WPC >= 3 ? 16 : 32;     // a whole chunk per set where the registers of two waves per SIMD allow it
+      const float* __restrict__ px = a.proj_x;
+      const int phw = a.proj_h * a.proj_w_in;
+      // 32-bit element offset from uniform bases (the entry point admits proj_x below 2^30 elements)
+      const unsigned xo = (unsigned)((ln * a.proj_c + 32 * hh) * phw + cur.ho * a.proj_stride * a.proj_w_in + cur.wo * a.proj_stride);
+      const int nsteps = a.proj_c / (2 * SZ);
+      auto first_channel = [&](int s) { return 64 * ((s * SZ) >> 5) + ((s * SZ) & 31); };      // (of lane half 0)
+      auto gather = [&](int s, float (&v)[SZ]) {
+        const float* __restrict__ src = px + (long long)first_channel(s) * phw;
+#pragma unroll
+        for (int m = 0; m < SZ; ++m) v[m] = (src + (long long)m * phw)[xo];
+      };
+      v16f pacc;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) pacc[i] = 0.f;
+      const float* __restrict__ wrow = &s_pw[col * pitch + 32 * hh];
+      auto mfmas = [&](int s, const float (&v)[SZ]) {
+        const float* __restrict__ wsrc = wrow + first_channel(s);
+#pragma unroll
+        for (int h = 0; h < SZ / 16; ++h) {
+          float4 wf[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) wf[q] = *reinterpret_cast<const float4*>(wsrc + 16 * h + 4 * q);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].x, v[16 * h + 4 * q + 0], pacc, 0, 0, 0);
+            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].y, v[16 * h + 4 * q + 1], pacc, 0, 0, 0);
+            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].z, v[16 * h + 4 * q + 2], pacc, 0, 0, 0);
+            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].w, v[16 * h + 4 * q + 3], pacc, 0, 0, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      float xa[SZ], xb[SZ];
+      gather(0, xa);
+      for (int s = 0; s < nsteps; s += 2) {
+        if (s + 1 < nsteps) gather(s + 1, xb);
+        __builtin_amdgcn_sched_barrier(0);
+        mfmas(s, xa);
+        if (s + 1 < nsteps) {
+          if (s + 2 < nsteps) gather(s + 2, xa);
+          __builtin_amdgcn_sched_barrier(0);
+          mfmas(s + 1, xb);
+        }
+      }
+      float4 pbv[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) pbv[g] = *reinterpret_cast<const float4*>(&s_pbias[ob + 8 * g]);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) rv[i] = pacc[i] + reinterpret_cast<const float*>(&pbv[i >> 2])[i & 3];
+    } else if (want_pre || want_post) {
       const float* __restrict__ rsrc = want_pre ? a.res_pre : a.res_post;
       if (a.res_stream) {           // (uniform) last use of a tensor that does not fit the Infinity Cache next to the output: lsq_xnor_conv.h
 #pragma unroll
@@ -583,8 +676,44 @@ int launch(const ConvArgs& a, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+// lsq_xnor_conv2d_proj: two activation planes, unchained, the projection shortcut in the residual registers (PROJ).  Same
+// grid as launch(): one workgroup per CU, every wave strides over the pixel tiles of its out-channel tile.  The projection
+// weights take dynamic LDS on top of the static tables (more than 64 KB in all at 512 channels: announced once per kernel).
+// Shape = (waves per workgroup, waves per SIMD): EIGHT waves, two per SIMD, 198 / 199 / 221 / 213 registers.  Twelve waves
+// at three per SIMD (168 registers) do not hold two sets of gathered x beside the first channel word of the main loop:
+// 36-132 bytes of scratch even with sets of 16, so that shape is not built.
+#ifndef LSQ_PROJ_SHAPE
+#define LSQ_PROJ_SHAPE 8, 2
+#endif
+template <int GG>
+int launch_proj(const ConvArgs& a, hipStream_t st) {
+  constexpr int kShape[2] = {LSQ_PROJ_SHAPE};
+  constexpr int NWAVES = kShape[0], WPC = kShape[1];
+  const long long ntiles = ((long long)a.N * a.Ho * a.Wo + 31) >> 5;
+  const int n_ot = a.O / 32;
+  long long gx = (256 + n_ot - 1) / n_ot;
+  if (gx * NWAVES > ntiles) gx = (ntiles + NWAVES - 1) / NWAVES;
+  auto kern = xnor_mfma_kernel<2, GG, 9, NWAVES, WPC, false, true, true>;
+  static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       32 * (kProjMaxChannels + 4) * (int)sizeof(float));
+  if (raised != hipSuccess) return (int)raised;
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), (size_t)32 * (a.proj_c + 4) * sizeof(float), st, a);
+  return (int)hipGetLastError();
+}
+
 template <int KX>
 int launch_gg(const ConvArgs& a, hipStream_t st) {
+  if constexpr (KX == 2) {
+    if (a.proj_x) {
+      switch (a.cg) {
+        case 64: return launch_proj<1>(a, st);
+        case 128: return launch_proj<2>(a, st);
+        case 256: return launch_proj<4>(a, st);
+        case 512: return launch_proj<8>(a, st);
+      }
+      return kXnorMfmaNotEligible;
+    }
+  }
   // (test hook lsq_debug_xnor_impl(2): rounds 2-5's int8 kernel, the fp4 kernel's comparator -- same bits; plain calls only)
   if (a.int8_mfma && !a.xunits && !a.nq_planes32) {
     switch (a.cg) {
@@ -605,10 +734,15 @@ int launch_gg(const ConvArgs& a, hipStream_t st) {
 
 }  // namespace
 
-int xnor_conv_mfma(const ConvArgs& a, int kx, int groups, hipStream_t st) {
+bool xnor_conv_mfma_eligible(const ConvArgs& a, int kx, int groups) {
   const long long total = (long long)a.N * a.Ho * a.Wo;
   if (groups != 1 || a.KH != 3 || a.KW != 3 || a.dw != 1 || a.O % 32 || total * a.O >= (1ll << 30) || a.xplane_words * kx >= (1ll << 30))
-    return kXnorMfmaNotEligible;
+    return false;
+  return (kx == 1 || kx == 2) && (a.cg == 64 || a.cg == 128 || a.cg == 256 || a.cg == 512);
+}
+
+int xnor_conv_mfma(const ConvArgs& a, int kx, int groups, hipStream_t st) {
+  if (!xnor_conv_mfma_eligible(a, kx, groups)) return kXnorMfmaNotEligible;
   return kx == 2 ? launch_gg<2>(a, st) : launch_gg<1>(a, st);
 }
 

@@ -3,6 +3,7 @@
 #   NAME   the library is liblsq_hip_$(NAME).so, its objects $(NAME)_<source>.o
 #   SRCS   its .hip files
 #   HDRS   what they include besides include/lsq_hip.h (a change to any of them rebuilds the objects)
+#   LDLIBS (optional) what the library links besides the HIP runtime
 # and includes this file:  make -C ml-quant_amd/csrc/<dir>  ->  ../../lib/liblsq_hip_$(NAME).so
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
@@ -19,7 +20,7 @@ $(OUTDIR)/$(NAME)_%.o: %.hip $(HDRS) $(ROOT)/include/lsq_hip.h
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) $(LDLIBS)
 
 clean:
 	rm -f $(OBJS) $(LIB)

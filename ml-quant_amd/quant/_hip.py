@@ -342,6 +342,48 @@ def xnor_conv2d(planes: torch.Tensor, kx: int, xscales: torch.Tensor, wbits: tor
 E_UNSUPPORTED = -6
 
 
+#: (projection input channels, out-channels) for which the fused launch measured faster on MI355X than lsq_pointwise_conv +
+#: lsq_xnor_conv2d (profiles/proj_fused.json); every other shape keeps the two launches
+PROJ_FUSED_SHAPES = frozenset({(64, 128), (128, 256), (256, 512)})
+
+
+def proj_fused_wins(cp: int, o: int) -> bool:
+    return (cp, o) in PROJ_FUSED_SHAPES
+
+
+def xnor_conv2d_proj(planes: torch.Tensor, kx: int, xscales: torch.Tensor, wbits: torch.Tensor, wsum: torch.Tensor,
+                     wscales: torch.Tensor, bias: Optional[torch.Tensor], geom: ConvGeom, y: torch.Tensor, proj: tuple,
+                     relu: bool = False, res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
+                     prelu: Optional[torch.Tensor] = None) -> bool:
+    """lsq_xnor_conv2d with the projection shortcut ``proj = (x, w [O, Cp], bias or None, stride, post)`` computed in the
+    epilogue's residual registers (include/lsq_hip_conv_proj.h): ``post`` False = it plays ``res_pre``, True = ``res_post``.
+    Returns False -- nothing launched, nothing written -- where the library refuses the call as unsupported (the caller runs
+    ``pointwise_conv`` + ``xnor_conv2d``: same bits)."""
+    px, pw, pb, stride, post = proj
+    px, pw = _f32c(px), _f32c(pw)
+    pb = None if pb is None else _f32c(pb)
+    act, slope = _act(relu, prelu, geom.O)
+    m = geom.C * geom.H * geom.W
+    cp = px.shape[1]
+    nres = (res_pre is not None) + (res_post is not None)
+    macs = y.numel() * (geom.C // geom.groups) * geom.KH * geom.KW * kx * wscales.shape[0]
+    pd = _sublibs.Proj(px.data_ptr(), pw.data_ptr(), ptr(pb), cp, px.shape[2], px.shape[3], int(stride), int(bool(post)))
+    lib()                                           # (liblsq_hip_conv_proj.so links liblsq_hip.so: the same loaded object)
+    # bytes: the convolution's own plus the projection's gathered input (one 4-byte value per output pixel and input channel);
+    # ops stay the binary MACs, so the line's matrix-core fraction keeps its meaning
+    with _on(y), (_Timed('lsq_xnor_conv2d', geom.N * kx * m // 8 + 4 * y.numel() * (1 + nres) + 4 * (y.numel() // geom.O) * cp,
+                         macs, f'C{geom.C}_H{geom.H}_s{geom.stride_h}', geom.N * kx * m // 8 + 4 * y.numel())
+                  if _timing is not None else _UNTIMED):
+        code = conv_proj_lib().lsq_xnor_conv2d_proj(planes.data_ptr(), kx, xscales.data_ptr(), wbits.data_ptr(), wsum.data_ptr(),
+                                                    wscales.shape[0], wscales.data_ptr(), ptr(bias), ctypes.byref(geom), act,
+                                                    ptr(slope), ptr(res_pre), ptr(res_post), ctypes.byref(pd), y.data_ptr(),
+                                                    stream_ptr(y.device))
+    if code == E_UNSUPPORTED:
+        return False
+    check(code, 'lsq_xnor_conv2d_proj')
+    return True
+
+
 def xnor_conv2d_chain(planes: torch.Tensor, xscales: Optional[torch.Tensor], x_units: Optional[torch.Tensor], x_alpha: float,
                       wbits: torch.Tensor, wsum: torch.Tensor, wscales: torch.Tensor, bias: Optional[torch.Tensor],
                       geom: ConvGeom, y: torch.Tensor, relu: bool = False, res_pre: Optional[torch.Tensor] = None,
@@ -598,6 +640,7 @@ conv_act_half_lib, conv_act_half_library_path, CONV_ACT_HALF_ABI_VERSION = _subl
 conv_half_lib, conv_half_library_path, CONV_HALF_ABI_VERSION = _sublib('conv_half')
 conv_train_lib, conv_train_library_path, CONV_TRAIN_ABI_VERSION = _sublib('conv_train')
 conv_train_half_lib, conv_train_half_library_path, CONV_TRAIN_HALF_ABI_VERSION = _sublib('conv_train_half')
+conv_proj_lib, conv_proj_library_path, CONV_PROJ_ABI_VERSION = _sublib('conv_proj')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21

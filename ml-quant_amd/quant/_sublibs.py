@@ -37,6 +37,13 @@ class ConvDgradPlan(ctypes.Structure):
     _fields_ = [(name, ctypes.c_int32) for name in ('kernel', 'classes', 'dead_classes', 'tap_steps')]
 
 
+class Proj(ctypes.Structure):
+    """Mirror of ``lsq_proj``: the projection shortcut lsq_xnor_conv2d_proj computes in its epilogue's residual registers."""
+
+    _fields_ = [('x', ctypes.c_void_p), ('w', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('C', ctypes.c_int32),
+                ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('stride', ctypes.c_int32), ('post', ctypes.c_int32)]
+
+
 gp = ctypes.POINTER(ConvGeom)
 
 # ---- liblsq_hip.so: {header: prototypes}; quant._hip.lib() applies both (ABI_VERSION and the LSQ_HIP_LIB override live there)
@@ -117,6 +124,8 @@ SUBLIBS = (
         'lsq_signw_conv2d_dgrad_half_plan': (i32, [vp, vp]),
         'lsq_signw_conv2d_dgrad_half_workspace_bytes': (sz, [vp, i32]),
         'lsq_signw_conv2d_dgrad_half': (i32, [vp, i32, vp, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, sz, vp])}),
+    _entry('conv_proj', '|lsq_xnor_conv2d_proj[a-z0-9_]*', {
+        'lsq_xnor_conv2d_proj': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, ctypes.POINTER(Proj), vp, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

@@ -48,6 +48,25 @@ import torch.nn.functional as F
 from quant.binary.hip_module import HipQuantModule
 
 
+class ProjectionShortcut:
+    """A residual operand of ``QuantConv2d.fused_forward`` given as its recipe instead of a tensor: the folded projection
+    shortcut ``conv2d(x, w[:, :, None, None], b, stride)`` of a down-sampling block (CUDA fp32 ``x`` [N, C, H, W], ``w`` [O, C],
+    channels multiples of 64).  Passed as ``res_pre`` or ``res_post``, it is computed inside the XNOR convolution where
+    lsq_xnor_conv2d_proj takes the call and by lsq_pointwise_conv in front of it elsewhere -- the same bits either way.
+    ``tensor()`` is that separate launch; ``self[rows]`` the shortcut of the samples ``rows`` alone (what a reader of the
+    residual of a few samples needs, e.g. a layer-by-layer check)."""
+
+    def __init__(self, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], stride: int) -> None:
+        self.x, self.w, self.b, self.stride = x.detach(), w, b, int(stride)
+
+    def tensor(self, rows=None) -> torch.Tensor:
+        from quant import _hip
+        return _hip.pointwise_conv(self.x if rows is None else self.x[rows], self.w, self.b, self.stride)
+
+    def __getitem__(self, rows) -> torch.Tensor:
+        return self.tensor(rows)
+
+
 class QuantConv2d(HipQuantModule, nn.Conv2d):
     """``Conv2d(x_quant(clamp(x)), w_quant(w))`` with schemes fp | ls-1 | ls-2 | ls-T | gf-k."""
 
@@ -192,6 +211,7 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                       res_ready: Optional[torch.cuda.Event] = None) -> torch.Tensor:
         """``act(self(pre_bn(x)) + res_pre) + res_post`` -- one residual-block half (quant/models/resnet.py:
         95-100, 182-190); ``act`` = ReLU (``relu=True``), PReLU (``prelu`` = the nn.PReLU weight) or identity.
+        One of the two residuals may be a ``ProjectionShortcut`` in place of a tensor.
         On the HIP path the eval-mode batch norm is folded into the quantizer's read and the non-linearity /
         shortcut additions into the convolution's epilogue, so none of them is a separate pass over HBM;
         elsewhere it is the plain composition of the modules."""
@@ -202,6 +222,10 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             # res_ready: the residual operands were produced on another stream (the projection shortcut, models/resnet.py);
             # the quantizer does not need them, the convolution's launch waits for the event
             return self._forward_hip(x, pre_bn, relu, res_pre, res_post, prelu, next_q, res_ready)
+        if isinstance(res_pre, ProjectionShortcut):
+            res_pre = res_pre.tensor()
+        if isinstance(res_post, ProjectionShortcut):
+            res_post = res_post.tensor()
         if res_ready is not None:
             torch.cuda.current_stream(x.device).wait_event(res_ready)
         y = self(x if pre_bn is None else pre_bn(x))
@@ -264,12 +288,28 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         keep = (planes, units, pre)
         return nxt, chain.PreQuant(conv, bn, planes, units, (n, self.out_channels, ho, wo), _hip.stream_ptr(device)), keep
 
+    def _proj_in_kernel(self, x: torch.Tensor, chain) -> bool:
+        """Whether this call ends in the plain XNOR launch that can compute a projection shortcut itself: fp32 input, binary
+        activations, not a chained 1-bit layer."""
+        return x.dtype == torch.float32 and self.x_quant != 'fp' and not (self.x_quant == 'ls-1' and chain.ENABLED)
+
     def _forward_hip(self, x: torch.Tensor, pre_bn: Optional[nn.BatchNorm2d] = None, relu: bool = False,
                      res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
                      prelu: Optional[torch.Tensor] = None, next_q: Optional[tuple] = None,
                      res_ready: Optional[torch.cuda.Event] = None) -> torch.Tensor:
         from quant import _hip
         from quant.binary import chain
+        # a ProjectionShortcut in a residual slot: only the plain two-plane XNOR call at the end computes it itself (at most
+        # one: the kernel has one residual array in registers); everywhere else it is a launch of its own, here
+        proj = None
+        if isinstance(res_post, ProjectionShortcut) and res_pre is None and self._proj_in_kernel(x, chain):
+            proj, res_post = (res_post, True), None
+        elif isinstance(res_pre, ProjectionShortcut) and self._proj_in_kernel(x, chain):
+            proj, res_pre = (res_pre, False), None
+        if isinstance(res_pre, ProjectionShortcut):
+            res_pre = res_pre.tensor()
+        if isinstance(res_post, ProjectionShortcut):
+            res_post = res_post.tensor()
         handed = chain.pending(x)                  # (an attribute of the tensor object: read before detach())
         x = x.detach()
         pre = None if pre_bn is None else self._folded_bn(pre_bn)
@@ -336,6 +376,16 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                     return y
         planes, scales = self._act_planes(x, geom, k, _hip, (geom.pad_h, geom.pad_w, self.groups), pre)
         join()
+        if proj is not None:
+            sc, post = proj
+            if _hip.xnor_conv2d_proj(planes, k, scales, wbits, wsum, wscales, bias, geom, y, (sc.x, sc.w, sc.b, sc.stride, post),
+                                     relu, res_pre, res_post, prelu):
+                self.last_act_scales = scales
+                return y
+            if post:                                     # refused: the two launches, same bits
+                res_post = sc.tensor()
+            else:
+                res_pre = sc.tensor()
         _hip.xnor_conv2d(planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu)
         self.last_act_scales = scales
         return y

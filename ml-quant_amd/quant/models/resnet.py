@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from quant import _hip
-from quant.binary.binary_conv import QuantConv2d
+from quant.binary.binary_conv import ProjectionShortcut, QuantConv2d
 
 non_linearity_map = {'relu': nn.ReLU, 'prelu': nn.PReLU, 'identity': nn.Identity}
 
@@ -217,8 +217,18 @@ class XnorBasicBlock(nn.Module):
         if _fusable(self, x):
             # eval on the GPU: bn -> quantizer and conv -> relu -> (+shortcut) each collapse into one
             # kernel pair (QuantConv2d.fused_forward); same arithmetic as the modular path below
-            sc, sc_ready = _shortcut_on_side_stream(self.shortcut, x)
             a1, a2 = _act_args(self.nonlin1), _act_args(self.nonlin2)
+            pj = _fused_projection(self.shortcut, x, self.conv1 if self.double_shortcut else self.conv2)
+            if pj is not None:
+                # the projection is computed inside the convolution that adds it (lsq_xnor_conv2d_proj): no launch of its
+                # own, and its result never goes to memory
+                nxt = self.__dict__.get('chain_next')
+                if self.double_shortcut:
+                    first = self.conv1.fused_forward(x, self.bn1, res_post=pj, next_q=(self.bn2, self.conv2), **a1)
+                    return self.conv2.fused_forward(first, self.bn2, res_post=first, next_q=nxt, **a2)
+                first = self.conv1.fused_forward(x, self.bn1, next_q=(self.bn2, self.conv2), **a1)
+                return self.conv2.fused_forward(first, self.bn2, res_pre=pj, next_q=nxt, **a2)
+            sc, sc_ready = _shortcut_on_side_stream(self.shortcut, x)
             # next_q: who quantizes the result next -- with 1-bit activations that quantizer runs in the producing
             # convolution's epilogue (quant.binary.chain); `chain_next` = the following block's (bn1, conv1), set by QResNet
             nxt = self.__dict__.get('chain_next')
@@ -233,6 +243,30 @@ class XnorBasicBlock(nn.Module):
             return self.nonlin2(self.conv2(self.bn2(first))) + first
         second = self.conv2(self.bn2(first)) + self.shortcut(x)
         return self.nonlin2(second)
+
+
+#: the projection shortcut of an XnorBasicBlock is computed inside the XNOR convolution whose epilogue adds it, for the shapes
+#: where that measured faster (quant._hip.PROJ_FUSED_SHAPES); False: a launch of its own in front, as before -- the same bits
+FUSE_PROJECTION = True
+
+
+def _fused_projection(shortcut: nn.Module, x: torch.Tensor, consumer: QuantConv2d):
+    """The ``ProjectionShortcut`` of a folded ``_ConvBN`` shortcut that the consumer's kernel can compute itself (the
+    conditions of ``_ConvBN.forward``'s kernel branch, two-plane binary activations, a shape the gate lists), else None."""
+    if not FUSE_PROJECTION or SIDE_STREAM_SHORTCUT or not isinstance(shortcut, _ConvBN):
+        return None
+    conv, bn = shortcut[0], shortcut[1]
+    if not _eval_fold_ok(shortcut, bn, x) or consumer.x_quant not in ('ls-2', 'ls-T'):
+        return None
+    if not (conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.groups == 1 and x.dim() == 4
+            and x.dtype == torch.float32 and conv.weight.dtype == torch.float32 and conv.stride[0] == conv.stride[1]
+            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
+            and max(x.numel(), x.numel() // conv.in_channels * conv.out_channels) < 2 ** 30):
+        return None
+    if not _hip.proj_fused_wins(conv.in_channels, conv.out_channels):
+        return None
+    w, b = _folded_conv_bn(shortcut, conv, bn)
+    return ProjectionShortcut(x, w.view(conv.out_channels, conv.in_channels), b, conv.stride[0])
 
 
 #: the projection shortcut (1x1 stride-2 convolution + batch norm, resnet.py:180-190 of the reference) does not depend on the
