@@ -3,14 +3,22 @@ that computes the projection shortcut of a down-sampling block in its residual r
 
 Reference: the two launches it replaces, lsq_pointwise_conv followed by lsq_xnor_conv2d with the projection's output as the
 residual tensor.  The fused kernel runs the same chain of fp32 MFMAs on the same operand pairs and the same epilogue, so every
-comparison is torch.equal -- no tolerance.  The shapes are the smallest that reach every path: tiles of 32 pixels that straddle
-images, a partial last tile, one / several tiles per wave, 4 / 8 / 16 out-channel tiles, 1 / 2 / 4 chunks of 64 projection
-channels, and a stride-1 consumer of a stride-2 projection."""
+comparison is torch.equal -- no tolerance.  CASES are the smallest shapes with tiles of 32 pixels that straddle images, a partial
+last tile, 4 / 8 / 16 out-channel tiles, 1 / 2 / 4 chunks of 64 projection channels, and a stride-1 consumer of a stride-2
+projection; every one of them launches ONE workgroup per out-channel tile, so no wave of theirs sees a second tile.
+
+The wave that walks on to a second and third tile (advance(), the next tile's request, xo / yoff and the gather recomputed), every
+projection channel count 64 .. 512 (odd step counts of the ping-pong gather; C = Cp = 512, the largest LDS request) and Cp != C
+are the cases of tests/golden/projection_cases.py (FUSED_CASES, CP_CASES; tests/test_projection_cases_host.py proves what they
+launch).  Besides the two launches they are held to an anchor that does not involve lsq_pointwise_conv: with integer-grid
+projection operands the shortcut is exact in fp64 and as fp32 in any summation order, and the fused result must equal the plain
+lsq_xnor_conv2d output combined with it by the epilogue's own single fp32 operations."""
 
 import pytest
 import torch
 
 import detgen
+import projection_cases as PC
 
 pytestmark = pytest.mark.gpu
 
@@ -32,9 +40,14 @@ def _hip():
     return _hip
 
 
-def _operands(name, scheme):
+ALL_CASES = {**CASES, **PC.FUSED_CASES, **PC.CP_CASES}
+MARGIN = 256            # floats on either side of a guarded output
+
+
+def _operands(name, scheme, grid=False):
+    """grid: the projection's x, w and bias on the integer grid of projection_cases.grid_operands (the shortcut is then exact)."""
     hip = _hip()
-    n, c, (h, w), s, o, cp, (hx, wx) = CASES[name]
+    n, c, (h, w), s, o, cp, (hx, wx) = ALL_CASES[name]
     geom = hip.make_geom(n, c, h, w, o, 3, 3, (s, s), (1, 1), (1, 1), 1)
     x = detgen.normal(f'proj.{name}.x', (n, c, h, w), scale=1.2).to(DEV)
     planes = torch.zeros((2 * hip.act_plane_words(geom),), dtype=torch.int64, device=DEV)
@@ -44,11 +57,16 @@ def _operands(name, scheme):
     wsc = wt.abs().mean(dim=(1, 2, 3))[None].contiguous()
     wbits, wsum = hip.pack_weight(wt, geom, wsc)
     ho, wo = hip.out_hw(geom)
+    if grid:
+        px = PC.grid_operands(f'proj.{name}.gpx', (n, cp, hx, wx), *PC.X_RANGE)
+        pw = PC.grid_operands(f'proj.{name}.gpw', (o, cp), *PC.W_RANGE)
+        pb = PC.grid_operands(f'proj.{name}.gpb', (o,), *PC.B_RANGE)
+    else:
+        px = detgen.normal(f'proj.{name}.px', (n, cp, hx, wx), scale=0.9)
+        pw = detgen.normal(f'proj.{name}.pw', (o, cp), scale=cp ** -0.5)
+        pb = detgen.normal(f'proj.{name}.pb', (o,), scale=0.3)
     return dict(hip=hip, geom=geom, planes=planes, xs=xs, wbits=wbits, wsum=wsum, wsc=wsc,
-                bias=detgen.normal(f'proj.{name}.b', (o,), scale=0.2).to(DEV),
-                px=detgen.normal(f'proj.{name}.px', (n, cp, hx, wx), scale=0.9).to(DEV),
-                pw=detgen.normal(f'proj.{name}.pw', (o, cp), scale=cp ** -0.5).to(DEV),
-                pb=detgen.normal(f'proj.{name}.pb', (o,), scale=0.3).to(DEV),
+                bias=detgen.normal(f'proj.{name}.b', (o,), scale=0.2).to(DEV), px=px.to(DEV), pw=pw.to(DEV), pb=pb.to(DEV),
                 slope=detgen.uniform(f'proj.{name}.slope', (o,), 0.05, 0.4).to(DEV), yshape=(n, o, ho, wo))
 
 
@@ -103,6 +121,97 @@ def test_two_runs_give_the_same_bits():
     first = _fused(cs, 'relu', True, True)
     second = _fused(cs, 'relu', True, True)
     assert torch.equal(first, second)
+
+
+# ---- waves that walk over several tiles, every Cp, the anchor (tests/golden/projection_cases.py) -------------------------------
+# (act, projection as res_post, projection bias)
+EPILOGUES = (('relu', True, True), ('prelu', False, True), ('none', True, False))
+MULTI = [(name, LS2) for name in PC.FUSED_CASES] + [(PC.FUSED_BOTH_SCHEMES, LST)]
+
+
+def _equals_two_launches(cs, where):
+    for act, post, with_bias in EPILOGUES:
+        want = _two_launches(cs, act, post, with_bias)
+        got = _fused(cs, act, post, with_bias)
+        assert not torch.isnan(want).any()
+        assert torch.equal(got, want), (where, act, post, with_bias, float((got - want).abs().max()))
+
+
+@pytest.mark.parametrize('name, scheme', MULTI, ids=[f'{n}-{"ls-2" if s == LS2 else "ls-T"}' for n, s in MULTI])
+def test_multi_tile_waves_equal_pointwise_then_xnor(name, scheme):
+    _equals_two_launches(_operands(name, scheme), (name, scheme))
+
+
+@pytest.mark.parametrize('name', list(PC.CP_CASES))
+def test_every_projection_channel_count_equals_pointwise_then_xnor(name):
+    _equals_two_launches(_operands(name, LS2), name)          # (_fused asserts that the call was taken: a refusal or a launch error fails)
+
+
+def test_two_runs_of_a_multi_tile_launch_give_the_same_bits():
+    cs = _operands(PC.FUSED_PARTIAL, LS2)
+    first = _fused(cs, 'relu', True, True)
+    second = _fused(cs, 'relu', True, True)
+    assert torch.equal(first, second)
+
+
+def _plain(cs, act):
+    """lsq_xnor_conv2d without any residual."""
+    y = torch.full(cs['yshape'], float('nan'), device=DEV)
+    cs['hip'].xnor_conv2d(cs['planes'], 2, cs['xs'], cs['wbits'], cs['wsum'], cs['wsc'], cs['bias'], cs['geom'], y, relu=act == 'relu',
+                          prelu=cs['slope'] if act == 'prelu' else None)
+    assert not torch.isnan(y).any()
+    return y
+
+
+def _shortcut_exact(cs, with_bias):
+    """The projection of integer-grid operands in fp64 (a strided slice and one matmul per image), cast to fp32: exact."""
+    xs = cs['px'][:, :, ::2, ::2].double()
+    n, cp, ho, wo = xs.shape
+    sc = torch.matmul(cs['pw'].double(), xs.reshape(n, cp, ho * wo)).reshape(cs['yshape'])
+    if with_bias:
+        sc = sc + cs['pb'].double().view(1, -1, 1, 1)
+    assert torch.equal(sc.float().double(), sc) and float(sc.abs().max()) < 2 ** 15
+    return sc.float()
+
+
+def _act(v, act, slope):
+    if act == 'relu':
+        return torch.relu(v)
+    if act == 'prelu':
+        return torch.where(v > 0, v, slope.view(1, -1, 1, 1) * v)
+    return v
+
+
+@pytest.mark.parametrize('name', list(PC.CP_CASES) + list(PC.FUSED_ANCHORED))
+def test_fused_equals_plain_xnor_combined_with_the_exact_shortcut(name):
+    """The anchor without lsq_pointwise_conv.  res_post: fused == plain(act) + sc; res_pre: fused == act(plain(no act) + sc) -- the
+    epilogue's own single fp32 operations (one add; max(., 0); one product with the channel's slope) on the same two fp32 values."""
+    cs = _operands(name, LS2, grid=True)
+    for with_bias in (True, False):
+        sc = _shortcut_exact(cs, with_bias)
+        for act in ('relu', 'prelu', 'none'):
+            got = _fused(cs, act, True, with_bias)
+            want = _plain(cs, act) + sc
+            assert torch.equal(got, want), (name, 'res_post', act, with_bias, float((got - want).abs().max()))
+        base = _plain(cs, 'none')
+        for act in ('relu', 'prelu'):
+            got = _fused(cs, act, False, with_bias)
+            want = _act(base + sc, act, cs['slope'])
+            assert torch.equal(got, want), (name, 'res_pre', act, with_bias, float((got - want).abs().max()))
+
+
+def test_multi_tile_launch_writes_all_of_y_and_nothing_else():
+    cs = _operands(PC.FUSED_PARTIAL, LS2)
+    hip = cs['hip']
+    want = _fused(cs, 'relu', True, True)
+    buf = torch.full((want.numel() + 2 * MARGIN,), float('nan'), device=DEV)
+    inside = buf[MARGIN:MARGIN + want.numel()]
+    assert inside.data_ptr() % 16 == 0
+    assert hip.xnor_conv2d_proj(cs['planes'], 2, cs['xs'], cs['wbits'], cs['wsum'], cs['wsc'], cs['bias'], cs['geom'],
+                                inside.view(cs['yshape']), (cs['px'], cs['pw'], cs['pb'], 2, True), relu=True)
+    assert torch.isnan(buf[:MARGIN]).all() and torch.isnan(buf[MARGIN + want.numel():]).all(), 'written outside y'
+    assert not torch.isnan(inside).any(), 'outputs left unwritten'
+    assert torch.equal(inside.view(cs['yshape']), want)
 
 
 def _conv_module(cin, cout, stride, seed):
