@@ -4,9 +4,10 @@ restatement and against fp32 arithmetic) and tests/test_gpu_conv_half.py (the ke
 here touches a GPU.
 
 Every case names the kernel it is there for (``plan``: the bits lsq_signw_conv2d_half_plan returns); the host test asserts
-that the library agrees.  ``fp32_patch`` restates the dispatch of lsq_signw_conv2d (csrc/lsq_signw_conv.hip, the lines under
-"Layers whose input patch fits the LDS planes take the patch kernel") without a pre-scale: where it is true that call takes
-its patch kernel or its 3x3 fast path, the two paths DESIGN 4.4 states to be bit-identical.
+that the library agrees.  ``fp32_patch`` restates patch_plan (csrc/lsq_signw_conv_core.h), the one rule by which both
+lsq_signw_conv2d and lsq_signw_conv2d_half choose between their patch and tiled kernels, without a pre-scale -- independently,
+in Python: it is the check on that function.  Where it is true lsq_signw_conv2d takes its patch kernel or its 3x3 fast path,
+the two paths DESIGN 4.4 states to be bit-identical.
 
 Sizes.  The patch of a workgroup is bounded for its full tile of pixels, whatever the batch: at stride 2 x 2 the 128 pixels
 of a NARROW tile (O / groups <= 64) need 254 entries for the pixels and (127 // Wo + 1) row gaps of 2 (Wp - Wo) entries.  Over
@@ -19,6 +20,7 @@ extras.  The general kernel's wide case needs a row of 600 pixels: a shorter one
 import collections
 import functools
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -94,7 +96,8 @@ def tile_pixels(c: Case) -> int:
 
 
 def fp32_patch(c: Case) -> bool:
-    """True where lsq_signw_conv2d, called without a pre-scale, takes its patch kernel or 3x3 fast path for ``c``."""
+    """True where lsq_signw_conv2d, called without a pre-scale, takes its patch kernel or 3x3 fast path for ``c``: patch_plan
+    of csrc/lsq_signw_conv_core.h, restated."""
     ho, wo = out_hw(c)
     hp, wp = c.H + 2 * c.pad[0], c.W + 2 * c.pad[1]
     pbn = tile_pixels(c)
@@ -218,3 +221,21 @@ def reference(cid: str, dt: str) -> torch.Tensor:
     w, _, sc, b = weights(cid)
     wq = P.quantize_weight(w, c.ws, sc)
     return F.conv2d(clamped(cid, dt).double(), wq.double(), None if b is None else b.double(), c.stride, c.pad, c.dil, c.groups)
+
+
+def im2col64(x, w, b, c: Case):
+    """y[n, o, ho, wo] = b[o] + sum over (channel of o's group, kh, kw) of xpad[n, ch, ho s + kh d, wo s + kw d] w[o, ch, kh, kw]
+    in fp64 (numpy arrays), tap by tap with strided slices: no convolution routine."""
+    ho, wo = out_hw(c)
+    cg, og = c.C // c.groups, c.O // c.groups
+    xp = np.zeros((c.N, c.C, c.H + 2 * c.pad[0], c.W + 2 * c.pad[1]))
+    xp[:, :, c.pad[0]:c.pad[0] + c.H, c.pad[1]:c.pad[1] + c.W] = x
+    y = np.zeros((c.N, c.O, ho, wo))
+    for g in range(c.groups):
+        for kh in range(c.KH):
+            for kw in range(c.KW):
+                r0, c0 = kh * c.dil[0], kw * c.dil[1]
+                win = xp[:, g * cg:(g + 1) * cg, r0:r0 + (ho - 1) * c.stride[0] + 1:c.stride[0],
+                         c0:c0 + (wo - 1) * c.stride[1] + 1:c.stride[1]]
+                y[:, g * og:(g + 1) * og] += np.einsum('nchw,oc->nohw', win, w[g * og:(g + 1) * og, :, kh, kw])
+    return y if b is None else y + b[None, :, None, None]

@@ -7,8 +7,7 @@ formula to autograd through the reference-equal torch formulation; tests/test_gp
 value bit for bit).  ``step64`` is the whole step in fp64 for GIVEN activation and weight scales: every decision of the
 chains (sign of d_i, |d_i| <= 1, inside the clamp) is made in fp32 exactly as the kernels make it, every value is fp64.
 
-``transposed_kernel`` restates the dispatch of lsq_signw_conv2d (csrc/lsq_signw_conv.hip, the lines under "Layers whose
-input patch fits the LDS planes take the patch kernel") for the role the convolution plays in the backward pass: input
+``transposed_kernel`` restates the dispatch of lsq_signw_conv2d (patch_plan of csrc/lsq_signw_conv_core.h) for the role the convolution plays in the backward pass: input
 channels = the layer's O, out-channels = the layer's C, unit stride over the zero-inserted gradient, padding k-1-p, a
 pre-scale always present and no prepared weights (so never the 3x3 fast path).
 """

@@ -181,22 +181,7 @@ def test_plan_pins_every_case_to_its_kernel_and_the_table_is_complete(hip):
         assert c.N * c.C * c.H * c.W <= 1 << 17 and c.N * c.O * C.out_hw(c)[0] * C.out_hw(c)[1] <= 1 << 17
 
 
-def _im2col64(x, w, b, c):
-    """y[n, o, ho, wo] = b[o] + sum over (channel of o's group, kh, kw) of xpad[n, ch, ho s + kh d, wo s + kw d] w[o, ch, kh, kw]
-    in fp64, tap by tap with strided slices: no convolution routine."""
-    ho, wo = C.out_hw(c)
-    cg, og = c.C // c.groups, c.O // c.groups
-    xp = np.zeros((c.N, c.C, c.H + 2 * c.pad[0], c.W + 2 * c.pad[1]))
-    xp[:, :, c.pad[0]:c.pad[0] + c.H, c.pad[1]:c.pad[1] + c.W] = x
-    y = np.zeros((c.N, c.O, ho, wo))
-    for g in range(c.groups):
-        for kh in range(c.KH):
-            for kw in range(c.KW):
-                r0, c0 = kh * c.dil[0], kw * c.dil[1]
-                win = xp[:, g * cg:(g + 1) * cg, r0:r0 + (ho - 1) * c.stride[0] + 1:c.stride[0],
-                         c0:c0 + (wo - 1) * c.stride[1] + 1:c.stride[1]]
-                y[:, g * og:(g + 1) * og] += np.einsum('nchw,oc->nohw', win, w[g * og:(g + 1) * og, :, kh, kw])
-    return y if b is None else y + b[None, :, None, None]
+_im2col64 = C.im2col64      # the sum written out tap by tap in fp64 (shared with tests/test_gpu_signw_conv_cases.py)
 
 
 @pytest.mark.parametrize('dt', C.DTYPES)

@@ -210,3 +210,16 @@ def test_the_shared_mma_header_is_a_prerequisite_of_the_objects_that_include_it(
         lines = compile_lines(sub)
         assert len(lines) == 1 and f'lsq_{sub}.hip' in lines[0] and f'{sub}_lsq_{sub}.o' in lines[0], (sub, lines)
     assert compile_lines('train') == []
+
+
+def test_the_shared_conv_core_is_a_prerequisite_of_both_libraries_that_instantiate_it():
+    """csrc/lsq_signw_conv_core.h holds the general sign-weight convolution of liblsq_hip.so and liblsq_hip_conv_half.so:
+    `make -n -W <header>` (a query) after a build must want to recompile lsq_signw_conv.o and conv_half's object."""
+    csrc = os.path.join(ROOT, 'ml-quant_amd', 'csrc')
+    header = os.path.join(csrc, 'lsq_signw_conv_core.h')
+    assert os.path.exists(header)
+    for sub, obj in (('', 'lsq_signw_conv.o'), ('conv_half', 'conv_half_lsq_conv_half.o')):
+        subprocess.run(['make', '-C', os.path.join(csrc, sub)], check=True, capture_output=True)     # (nothing to do after build())
+        out = subprocess.run(['make', '-n', '-W', header, '-W', os.path.basename(header), '-C', os.path.join(csrc, sub)],
+                             check=True, capture_output=True, text=True).stdout      # (the Makefiles spell it both ways)
+        assert any(' -c ' in line and obj in line for line in out.splitlines()), (sub, out)
