@@ -632,6 +632,7 @@ train_lib, train_library_path, TRAIN_ABI_VERSION = _sublib('train')
 linear_lib, linear_library_path, LINEAR_ABI_VERSION = _sublib('linear')
 linear_fp_lib, linear_fp_library_path, LINEAR_FP_ABI_VERSION = _sublib('linear_fp')
 linear_train_lib, linear_train_library_path, LINEAR_TRAIN_ABI_VERSION = _sublib('linear_train')
+linear_train_half_lib, linear_train_half_library_path, LINEAR_TRAIN_HALF_ABI_VERSION = _sublib('linear_train_half')
 linear_wgrad_lib, linear_wgrad_library_path, LINEAR_WGRAD_ABI_VERSION = _sublib('linear_wgrad')
 linear_half_lib, linear_half_library_path, LINEAR_HALF_ABI_VERSION = _sublib('linear_half')
 linear_act_half_lib, linear_act_half_library_path, LINEAR_ACT_HALF_ABI_VERSION = _sublib('linear_act_half')
@@ -647,6 +648,7 @@ LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
 LINEAR_WGRAD_MAX_SAMPLES = 65535    # lsq_linear_signx_wgrad: N <= 65535 (the limit of lsq_quant_values)
 LINEAR_HALF_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}     # LSQ_DTYPE_*
 CONV_DGRAD_HALF_MAX_SAMPLES = 65535    # lsq_signw_conv2d_dgrad_half with x: N <= 65535 (the limit of lsq_ste_backward)
+LINEAR_DGRAD_HALF_MAX_SAMPLES = 65535  # lsq_linear_signw_dgrad_half with x: M / T <= 65535 (the same limit)
 
 
 # ---- the training library (include/lsq_hip_train.h)
@@ -811,6 +813,63 @@ def linear_signw_dgrad(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Ten
                          2 * 2 * M * F * O * kw):       # bf16 FLOPs: the hi and the lo pass of every plane
         check(tl.lsq_linear_signw_dgrad(gy.data_ptr(), wbits.data_ptr(), kw, wscales.data_ptr(), M, F, O, gx.data_ptr(),
                                         *_ws_args(ws), stream_ptr(dev)), 'lsq_linear_signw_dgrad')
+    return gx
+
+
+# ---- the linear layer's 16-bit training library (include/lsq_hip_linear_train_half.h)
+def linear_signw_dgrad_half(gy: torch.Tensor, wbits: torch.Tensor, wscales: torch.Tensor, M: int, F: int, O: int,
+                            x: Optional[torch.Tensor] = None, xscales: Optional[torch.Tensor] = None, alpha: float = -1.0,
+                            T: int = 1, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """grad_x [M, F] of the 16-bit train step in one launch (lsq_linear_signw_dgrad_half): gy @ w_q for the bf16 / fp16
+    gradient rows ``gy`` [M, O] (any 2-byte-aligned data pointer) and the forward's own sign planes ``wbits`` / fp32 scales
+    ``wscales`` [kw, O]; with ``x`` (the step's input [M, F] of gy's type, sample n owning rows n T .. n T + T - 1) the
+    result then goes through the straight-through estimator of the activation quantizer -- ``xscales`` [kx, M / T] fp32, None
+    for fp activations -- and the clamp ``alpha``, the bound ALREADY ROUNDED into the type (negative: none).  ``out_dtype``:
+    gy.dtype (the default) or torch.float32; the 16-bit result is the fp32 one rounded once.  With ``x`` there are at most
+    65535 samples (the limit of lsq_ste_backward).  The transposed plane image lives in the workspace of
+    ``linear_signw_dgrad`` (the same size; cached per (device, stream), rewritten by every call; kernels of one stream run in
+    order)."""
+    what = 'lsq_linear_signw_dgrad_half'
+    M, F, O, T = int(M), int(F), int(O), int(T)
+    _check_half(what, 'gy', gy)
+    out_dtype = gy.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, gy.dtype):
+        raise TypeError(f'{what}: out_dtype must be torch.float32 or {gy.dtype}, got {out_dtype}')
+    if x is not None and x.dtype != gy.dtype:
+        raise TypeError(f'{what}: x must be of gy\'s type {gy.dtype}, got {x.dtype}')
+    if xscales is not None and x is None:
+        raise ValueError(f'{what}: xscales without x')
+    dims = {'M': M, 'F': F, 'O': O} if x is None else {'M': M, 'F': F, 'O': O, 'T': T}
+
+    def mismatch():
+        if xscales is not None and (xscales.dim() != 2 or not 1 <= xscales.shape[0] <= MAX_PLANES
+                                    or xscales.shape[1] != M // T):
+            return 'activation scales and (kx, M / T)'
+        if not 1 <= wscales.shape[0] <= MAX_PLANES:
+            return f'{wscales.shape[0]} weight planes and 1 .. {MAX_PLANES}'
+        if x is not None and M // T > LINEAR_DGRAD_HALF_MAX_SAMPLES:
+            return f'{M // T} samples and the limit of {LINEAR_DGRAD_HALF_MAX_SAMPLES} with x'
+
+    _check_linear(what, dims, {'wscales': wscales} if xscales is None else {'wscales': wscales, 'xscales': xscales},
+                  {'wbits': wbits}, bad=gy.numel() != M * O or (x is not None and (x.numel() != M * F or (T > 0 and M % T != 0))),
+                  wplanes=(wbits, wscales, F, O), mismatch=mismatch)
+    dev = wscales.device
+    halves = [gy] if x is None else [gy, x]
+    if any(not t.is_contiguous() for t in halves):
+        raise ValueError(f'{what}: operands must be contiguous')
+    if any(t.device != dev for t in halves):
+        raise ValueError(f'{what}: every operand on the same cuda device')
+    kw, nw, opad = wscales.shape[0], (F + 63) // 64, (O + 15) // 16 * 16
+    tl = linear_train_half_lib()
+    need = int(tl.lsq_linear_signw_dgrad_half_workspace_bytes(kw, F, O))
+    ws = _stream_buffer('linear_dgrad', need, dev) if need else None
+    gx = torch.empty((M, F), dtype=out_dtype, device=dev)
+    kx = 0 if xscales is None else xscales.shape[0]
+    nbytes = 2 * M * O * kw + 8 * kw * nw * opad + 2 * need + gx.element_size() * M * F + (0 if x is None else 2 * M * F)
+    with _on(gx), (_Timed(what, nbytes, 2 * 2 * M * F * O * kw) if _timing is not None else _UNTIMED):      # (hi and lo pass)
+        check(tl.lsq_linear_signw_dgrad_half(gy.data_ptr(), LINEAR_HALF_DTYPES[gy.dtype], wbits.data_ptr(), kw,
+                                             wscales.data_ptr(), M, F, O, ptr(x), T, kx, ptr(xscales), float(alpha),
+                                             gx.data_ptr(), LINEAR_HALF_DTYPES[out_dtype], *_ws_args(ws), stream_ptr(dev)), what)
     return gx
 
 

@@ -100,6 +100,9 @@ SUBLIBS = (
     _entry('linear_train', '|lsq_linear_signw_dgrad[a-z0-9_]*', {
         'lsq_linear_signw_dgrad': (i32, [vp, vp, i32, vp, i64, i64, i64, vp, vp, sz, vp]),
         'lsq_linear_signw_dgrad_workspace_bytes': (sz, [i32, i64, i64])}),
+    _entry('linear_train_half', '|lsq_linear_signw_dgrad_half[a-z0-9_]*', {
+        'lsq_linear_signw_dgrad_half_workspace_bytes': (sz, [i32, i64, i64]),
+        'lsq_linear_signw_dgrad_half': (i32, [vp, i32, vp, i32, vp, i64, i64, i64, vp, i64, i32, vp, f32, vp, i32, vp, sz, vp])}),
     _entry('linear_wgrad', '|lsq_linear_signx_wgrad[a-z0-9_]*', {
         'lsq_linear_signx_wgrad': (i32, [vp, vp, i32, vp, f32, i64, i64, i64, i64, vp, vp, sz, vp]),
         'lsq_linear_signx_wgrad_workspace_bytes': (sz, [i32, i64, i64, i64, i64])}),

@@ -39,7 +39,13 @@ Dispatch of ``forward``:
     the same limits -> the kernels of the inference path for the forward and ``quant.binary.hip_train_linear`` for the
     backward (lsq_linear_signw_dgrad of liblsq_hip_linear_train.so, straight-through estimator), one
     ``torch.autograd.Function`` per call.
-  * anything else (CPU, training without ``hip_train``, ``fp`` weights, 16-bit weights, a 16-bit input with free-running
+  * CUDA bf16 / fp16 tensor in ``train()`` mode with ``hip_train_half`` set (class attribute, False by default; ``hip_train``
+    is not needed), binary fp32 weights, autocast off or set to the input's own type, at most 65535 samples and the same
+    limits (the ``act_half_solve`` gate is an eval switch and does not apply) -> ``hip_train_linear._QuantLinearStepHalf``:
+    lsq_act_quant_half on (N, T*F, 1, 1) + lsq_linear_xnor, or lsq_linear_signw_half, for the forward (y in the input's
+    type), ONE lsq_linear_signw_dgrad_half (liblsq_hip_linear_train_half.so) for grad_x in the input's type, grad_w and
+    grad_b in fp32.  A missing library raises: the switch asked for the kernel.
+  * anything else (CPU, training without ``hip_train`` / a 16-bit input without ``hip_train_half``, ``fp`` weights, 16-bit weights, a 16-bit input with free-running
     ``ls-2`` / ``ls-T`` activations without ``act_half_solve`` or under an autocast of another type, F % 64 != 0 with T > 1 for binary activations, beyond the kernels'
     limits) -> the torch formulation ``F.linear(x_approximate(clamp(x)), w_approximate(w), bias)`` on
     the same 4-D views.
@@ -81,12 +87,18 @@ class QuantLinear(HipQuantModule, nn.Linear):
     #: default until the kernel is measured against the cast route
     act_half_solve = False
 
+    #: a bf16 / fp16 train-mode CUDA tensor -- what the layer is handed under torch.autocast('cuda', torch.bfloat16) -- through
+    #: the kernels: ``hip_train_linear._QuantLinearStepHalf`` on lsq_linear_signw_dgrad_half.  A switch of its own (it does not
+    #: need ``hip_train``, which alone governs fp32 inputs).  False: the torch formulation
+    hip_train_half = False
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
             return self._forward_hip(x)
-        if self.training and self.hip_train and x.is_cuda:
+        if self.training and x.is_cuda and (self.hip_train or self.hip_train_half):
             from quant.binary import hip_train_linear
-            if hip_train_linear.supported(self, x):
+            # (fp32 inputs are hip_train's alone; supported() asks hip_train_half for a 16-bit one)
+            if (self.hip_train or x.dtype != torch.float32) and hip_train_linear.supported(self, x):
                 return hip_train_linear.train_step_forward(self, x)
         return self._forward_torch(x)
 
@@ -120,10 +132,11 @@ class QuantLinear(HipQuantModule, nn.Linear):
             return False                  # (a 16-bit input under an autocast of another type: torch decides the types)
         return self._hip_supports(x)
 
-    def _hip_supports(self, x: torch.Tensor) -> bool:
+    def _hip_supports(self, x: torch.Tensor, train_step: bool = False) -> bool:
         """The limits of lsq_act_quant / lsq_linear_act_quant_half / lsq_linear_act_quant_solve_half and lsq_linear_xnor (binary activations, fp32 / bf16 and
         fp16) or of lsq_linear_signw / lsq_linear_signw_half (fp activations, fp32 / bf16 and fp16); anything outside them
-        takes the torch formulation."""
+        takes the torch formulation.  ``train_step``: the eval switch ``act_half_solve`` does not apply (the 16-bit train step
+        solves free-running ls-2 / ls-T on lsq_act_quant_half)."""
         from quant import _hip
         if self.weight.dtype != torch.float32:
             return False
@@ -143,7 +156,7 @@ class QuantLinear(HipQuantModule, nn.Linear):
             return False
         if self.x_quant in ('ls-2', 'ls-T') and (row + self.act_skip - 1) // self.act_skip >= _hip.MAX_SOLVER_KEYS:
             return False
-        if (x.dtype != torch.float32 and self.x_quant in ('ls-2', 'ls-T') and not self.act_half_solve
+        if (not train_step and x.dtype != torch.float32 and self.x_quant in ('ls-2', 'ls-T') and not self.act_half_solve
                 and self.x_approximate.eval_scales(n) is None):
             return False                  # (the free-running 16-bit scale solve is off by default: DESIGN 4.17)
         return True
