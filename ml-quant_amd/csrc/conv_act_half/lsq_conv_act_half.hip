@@ -20,31 +20,24 @@
 //     on (C, H, W, groups) alone -- not on N, the sample's position, the address or the call.  v_q = (float)(S_q / M).
 //   * PASSES: ls-1 / gf-1 -> one sweep.  gf-k -> k sweeps (the row again from L2), sweep q writes plane q.  Given scales ->
 //     one sweep for k <= 2 (both planes), k sweeps of one plane beyond (k x PIX words would not fit a lane's registers).
-//   * ls-2 / ls-T free-running: the count table of lsq_linear_act_solve.hip (one count per 15-bit magnitude key, dynamic LDS
-//     bounded by key(alpha), swizzled index) over the flat sub-sample row[::skip], its plan / test / argmin on
-//     lsq_solver_math.h, then one sweep for both planes and S_1.  Only these kernels carry the table.
+//   * ls-2 / ls-T free-running: solve_v1 of linear_act_solve/lsq_half_table.h -- the count table (one count per
+//     15-bit magnitude key, dynamic LDS bounded by key(alpha), swizzled index) over the flat sub-sample row[::skip], its plan /
+//     test / argmin on lsq_solver_math.h; lsq_linear_act_solve.hip holds the same statements in line --, then one sweep for both
+//     planes and S_1.  Only these kernels carry the table.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "lsq_hip_conv_act_half.h"
-#include "../lsq_half_rows.h"
-#include "../lsq_solver_math.h"
+#include "../linear_act_solve/lsq_half_table.h"
 
 namespace {
 
 using namespace lsq_half;                             // to_f32, clamp_sym, load_group, wave_sum
-using lsq::Best;
-using lsq::kNoKey;
+using namespace lsq_half_table;                       // Shared, solve_v1, Best, kNoKey, top_key, table_bytes, allow_full_table
 
-constexpr int kThreads = 1024, kWaves = kThreads / 64;
-constexpr unsigned kKeys = 1u << 15;                  // magnitudes of a 16-bit type
-constexpr unsigned kSlice = 64;                       // keys of a slice: one thread in the plan, one wave in the exact test
-constexpr int kSlices = (int)(kKeys / kSlice);        // 512: the first half of the workgroup plans, every wave tests
-static_assert(kSlices <= kThreads, "one slice per thread");
+constexpr int kThreads = 1024, kWaves = kThreads / 64;   // (the first 512 threads plan the table's slices, every wave tests)
 constexpr int kBatch = 8;                             // loads a lane requests before it consumes any of them
 constexpr int kMaxSplitLog2 = 3;                      // at most 8 lanes an item: a lane keeps whole groups of 8 channels
 
@@ -64,23 +57,6 @@ struct Args {
   unsigned kmax;                      // the largest key a clamped value has; the table holds the slices up to it
   float alpha;                        // clamp bound (negative: none)
 };
-
-struct Shared {                       // (kSolve only)
-  unsigned first[kSlices];            // first non-empty key of slice t (kNoKey: the slice is empty)
-  unsigned next[kSlices];             // first non-empty key above slice t (kNoKey: none)
-  unsigned r0[kSlices];               // sorted position of slice t's first element
-  double p0[kSlices];                 // sum of the elements below slice t
-  unsigned listed[kSlices];           // slices that may hold a candidate
-  unsigned nlisted;
-  unsigned wcnt[kWaves];
-  double wsum[kWaves];
-  Best wbest[kWaves];
-};
-
-__device__ __forceinline__ unsigned phys(unsigned key) { return key ^ ((key >> 6) & 31u); }
-
-template <bool F16>
-__device__ __forceinline__ double key_value(unsigned key) { return (double)to_f32<F16>(key); }
 
 // PIX consecutive elements as 16-bit halves of 32-bit words
 template <int PIX>
@@ -215,200 +191,6 @@ __device__ __forceinline__ double block_sum(double acc, double* slot) {
   return tot;
 }
 
-// The optimal v1 of the flat sub-sample xrow[::skip] on the count table: pass 1, plan, test and argmin of
-// lsq_linear_act_solve.hip, the same arithmetic in the same order.  Every thread returns the same candidate;
-// order == kNoKey: the row had none (value 0).
-template <bool F16, bool VEC16>
-__device__ __forceinline__ Best solve_v1(const Args& a, const unsigned short* __restrict__ xrow, unsigned* hist, Shared& sh) {
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const unsigned slices = a.kmax / kSlice + 1u;       // <= kSlices
-  const unsigned n = a.n;
-  const bool ternary = a.ternary != 0;
-  for (unsigned i = tid; i < slices * kSlice; i += kThreads) hist[i] = 0u;
-  if (tid == 0) sh.nlisted = 0u;
-  __syncthreads();
-
-  // ---- pass 1: the sub-sample into the table
-  unsigned c_zero = 0u, c_top = 0u;
-  auto count = [&](unsigned h) {
-    const unsigned key = min(h & 0x7FFFu, a.kmax);    // the key of the clamped value; no bit pattern leaves the table
-    if (key == 0u) ++c_zero;
-    else if (key == a.kmax) ++c_top;
-    else atomicAdd(&hist[phys(key)], 1u);
-  };
-  if constexpr (VEC16) {                              // (the sample starts on 16 bytes and M % 8 == 0)
-    const int G = (int)(a.M / 8);
-    for (int g = tid; g < G; g += kThreads) {
-      const uint4 raw = load_group<true>(xrow, a.M, g);
-      const unsigned d[4] = {raw.x, raw.y, raw.z, raw.w};
-      const unsigned r = (unsigned)((8ll * g) % a.skip);
-      unsigned pick = r ? (unsigned)a.skip - r : 0u;  // the group's first sub-sampled element
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if ((unsigned)j == pick) {
-          count((d[j >> 1] >> (16 * (j & 1))) & 0xFFFFu);
-          pick += (unsigned)a.skip;
-        }
-      }
-    }
-  } else {
-    for (unsigned s = tid; s < n; s += kThreads) count(xrow[(long long)s * a.skip]);
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    c_zero += __shfl_xor(c_zero, d);
-    c_top += __shfl_xor(c_top, d);
-  }
-  if (lane == 0) {
-    if (c_zero) atomicAdd(&hist[0], c_zero);
-    if (c_top) atomicAdd(&hist[phys(a.kmax)], c_top);
-  }
-  __syncthreads();
-
-  // ---- plan: every slice's count and sum, then their prefixes in slice order
-  unsigned cnt = 0u, first = kNoKey, last = 0u;
-  double sum = 0.0;
-  if ((unsigned)tid < slices) {
-    for (unsigned i = 0; i < kSlice; ++i) {
-      const unsigned k = (unsigned)tid * kSlice + i;
-      const unsigned c = hist[phys(k)];
-      if (c) {
-        if (first == kNoKey) first = k;
-        last = k;
-        cnt += c;
-        sum += (double)c * key_value<F16>(k);
-      }
-    }
-  }
-  unsigned ic = cnt;
-  double is = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned oc = __shfl_up(ic, d);
-    const double os = __shfl_up(is, d);
-    if (lane >= d) {
-      ic += oc;
-      is += os;
-    }
-  }
-  unsigned ex_c = __shfl_up(ic, 1);
-  double ex_s = __shfl_up(is, 1);
-  if (lane == 0) {
-    ex_c = 0u;
-    ex_s = 0.0;
-  }
-  if (lane == 63) {
-    sh.wcnt[wid] = ic;
-    sh.wsum[wid] = is;
-  }
-  if (tid < kSlices) sh.first[tid] = first;
-  __syncthreads();
-  unsigned r0 = ex_c;
-  double p0 = ex_s, total = 0.0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    if (w < wid) {
-      r0 += sh.wcnt[w];
-      p0 += sh.wsum[w];
-    }
-    total += sh.wsum[w];
-  }
-
-  // ---- test: slices as a whole, conservatively
-  unsigned nk = kNoKey;
-  if (cnt)
-    for (unsigned t = (unsigned)tid + 1u; t < slices && nk == kNoKey; ++t) nk = sh.first[t];
-  if (tid < kSlices) {
-    sh.next[tid] = nk;
-    sh.r0[tid] = r0;
-    sh.p0[tid] = p0;
-  }
-  if (cnt && n >= 3u) {
-    const double next_hi = nk != kNoKey ? key_value<F16>(nk) : (double)INFINITY;
-    if (lsq::may_hold_candidate(r0, cnt, p0, sum, key_value<F16>(first), key_value<F16>(last), next_hi, n, total, ternary))
-      sh.listed[atomicAdd(&sh.nlisted, 1u)] = (unsigned)tid;
-  }
-  __syncthreads();
-
-  // ---- the listed slices exactly: a wave a slice, a lane a key
-  Best best;
-  best.cost = (double)INFINITY;
-  best.order = kNoKey;
-  best.value = 0.f;
-  const unsigned nl = sh.nlisted;
-  for (unsigned s = (unsigned)wid; s < nl; s += kWaves) {
-    const unsigned t = sh.listed[s];
-    const unsigned k = t * kSlice + (unsigned)lane;
-    const unsigned c = hist[phys(k)];
-    const double v = key_value<F16>(k);
-    unsigned jc = c;
-    double js = (double)c * v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned oc = __shfl_up(jc, d);
-      const double os = __shfl_up(js, d);
-      if (lane >= d) {
-        jc += oc;
-        js += os;
-      }
-    }
-    unsigned below_c = __shfl_up(jc, 1);
-    double below_s = __shfl_up(js, 1);
-    if (lane == 0) {
-      below_c = 0u;
-      below_s = 0.0;
-    }
-    const unsigned long long filled = __ballot(c != 0u);
-    const unsigned long long above = lane < 63 ? filled >> (lane + 1) : 0ull;
-    const unsigned succ = above ? k + (unsigned)__ffsll((long long)above) : sh.next[t];
-    const double succ_v = succ != kNoKey ? key_value<F16>(succ) : (double)INFINITY;
-    const unsigned run_r0 = sh.r0[t] + below_c;
-    const double run_p0 = sh.p0[t] + below_s;
-    if (c && lsq::run_has_candidate(v, c, run_r0, run_p0, succ_v, n, total, ternary)) {
-      Best cb;
-      cb.cost = lsq::cost_of(v, run_r0, run_p0, c, n, total, ternary);
-      cb.order = run_r0;
-      cb.value = (float)v;
-      if (lsq::better(cb, best)) best = cb;
-    }
-  }
-  // the ternary scheme's extra candidate (optimal.py:86-118: min > mean / 2 adds fl32(mean) / 2)
-  if (ternary && tid == 0) {
-    unsigned minkey = kNoKey;
-    for (unsigned t = 0; t < slices && minkey == kNoKey; ++t) minkey = sh.first[t];
-    const double mean = total / (double)n;
-    if (minkey != kNoKey && key_value<F16>(minkey) > 0.5 * mean) {
-      const float half = (float)((double)((float)mean) / 2.0);
-      Best cb;
-      cb.cost = lsq::cost_of((double)half, 0u, 0.0, 0u, n, total, true);
-      cb.order = n + 1u;
-      cb.value = half;
-      if (lsq::better(cb, best)) best = cb;
-    }
-  }
-  // workgroup argmin: `better` is a total order on (cost, order), so every lane ends with the same candidate
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    Best o;
-    o.cost = __shfl_xor(best.cost, d);
-    o.order = __shfl_xor(best.order, d);
-    o.value = __shfl_xor(best.value, d);
-    if (lsq::better(o, best)) best = o;
-  }
-  if (lane == 0) sh.wbest[wid] = best;
-  __syncthreads();
-  best = sh.wbest[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) {
-    const Best o = sh.wbest[w];
-    if (lsq::better(o, best)) best = o;
-  }
-  // a sub-sample of zeros only (+-0): its candidates are all 0, so it is reported as a row without one (v1 = 0 either way;
-  // `total` is the same bits in every thread)
-  if (!(total > 0.0)) best.order = kNoKey;
-  return best;
-}
-
 template <bool F16, int PIX, bool VEC, int MODE>
 __global__ __launch_bounds__(kThreads) void conv_quant_rows(Args a) {
   __shared__ double s_red[LSQ_MAX_PLANES][kWaves];    // (one slot per sweep: one barrier per sweep)
@@ -444,8 +226,12 @@ __global__ __launch_bounds__(kThreads) void conv_quant_rows(Args a) {
     if (tid == 0 && a.status) a.status[row] = 1;
   } else {
     extern __shared__ __attribute__((aligned(16))) unsigned hist[];   // [slices * 64] counts, swizzled by phys()
-    __shared__ Shared sh;
-    const Best best = solve_v1<F16, PIX == 8 && VEC>(a, xrow, hist, sh);
+    __shared__ Shared<kThreads> sh;
+    double total;
+    Best best = solve_v1<F16, PIX == 8 && VEC, kThreads>(a, xrow, a.M, hist, sh, total);
+    // a sub-sample of zeros only (+-0): its candidates are all 0, so it is reported as a sample without one (v1 = 0 either
+    // way; `total` is the same bits in every thread)
+    if (!(total > 0.0)) best.order = kNoKey;
     v[0] = best.value;                                // 0 where the row has no candidate
     const double acc = sweep<F16, PIX, VEC, 2, true>(a, xrow, prow, 1, v);
     const double tot = block_sum(acc, s_red[0]);
@@ -457,39 +243,14 @@ __global__ __launch_bounds__(kThreads) void conv_quant_rows(Args a) {
   }
 }
 
-// the largest key whose value is <= alpha (alpha >= 0): the key of the clamp bound where the bound is a value of the type
-template <bool F16>
-unsigned key_of_bound(float alpha) {
-  auto value = [](unsigned key) {
-    if constexpr (F16) return (float)__builtin_bit_cast(_Float16, (unsigned short)key);
-    else return __builtin_bit_cast(float, key << 16);
-  };
-  unsigned lo = 0u, hi = F16 ? 0x7C00u : 0x7F80u;     // 0 .. +inf
-  while (lo < hi) {
-    const unsigned mid = (lo + hi + 1u) >> 1;
-    if (value(mid) <= alpha) lo = mid; else hi = mid - 1u;
-  }
-  return lo;
-}
-
 template <bool F16, int PIX, bool VEC, int MODE>
 int launch(Args a, hipStream_t st) {
   unsigned lds = 0u;
   if constexpr (MODE == kSolve) {
-    a.kmax = a.alpha >= 0.f ? key_of_bound<F16>(a.alpha) : kKeys - 1u;
-    lds = (a.kmax / kSlice + 1u) * kSlice * 4u;
-    // dynamic LDS above 64 KiB needs the function attribute, once per device
-    static std::atomic<unsigned long long> allowed{0ull};
-    int dev = 0;
-    hipError_t rc = hipGetDevice(&dev);
+    a.kmax = top_key<F16>(a.alpha);
+    lds = table_bytes(a.kmax);
+    const hipError_t rc = allow_full_table<&conv_quant_rows<F16, PIX, VEC, MODE>>();
     if (rc != hipSuccess) return (int)rc;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(allowed.load(std::memory_order_acquire) & bit)) {
-      rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_quant_rows<F16, PIX, VEC, MODE>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kKeys * 4u));
-      if (rc != hipSuccess) return (int)rc;
-      allowed.fetch_or(bit, std::memory_order_release);
-    }
   }
   // One workgroup a sample, N < 2^31 workgroups: the hardware takes them in turn.
   hipLaunchKernelGGL((conv_quant_rows<F16, PIX, VEC, MODE>), dim3((unsigned)a.N), dim3(kThreads), lds, st, a);

@@ -19,6 +19,8 @@
 //            listed, and a wave takes a listed slice with one key per lane: run_has_candidate (exact divisions) on each
 //            non-empty key against the next non-empty key's value, cost_of, better.  The ternary extra candidate, then the
 //            workgroup argmin over (cost, first sorted position of the run): the order of the list does not matter.
+// (kSlice, phys(), key_value and the host helpers are lsq_half_table.h's; pass 1 to the argmin below is the text of its
+// solve_v1 written in line: calling it here changed this kernel's instruction stream and cost time)
 //   PASS 2   the row again (from L2): plane 0, plane 1 and S_1 by the per-group code of lsq_linear_act_quant_half's pass q = 1
 //            with v_0 = v1; the same summation rule (fp32 in a group, fp64 across groups: thread, wave butterfly, waves in order).
 
@@ -26,22 +28,21 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "lsq_hip_linear_act_solve.h"
-#include "../lsq_half_rows.h"
-#include "../lsq_solver_math.h"
+#include "lsq_half_table.h"
 
 namespace {
 
 using namespace lsq_half;                             // to_f32, clamp_sym, load_group, wave_sum
 using lsq::Best;
 using lsq::kNoKey;
+namespace table = lsq_half_table;                     // what this file shares with lsq_conv_act_half.hip
+using table::kSlice;
+using table::phys;
+using table::key_value;
 
 constexpr int kThreads = 512, kWaves = kThreads / 64;
-constexpr unsigned kKeys = 1u << 15;                  // magnitudes of a 16-bit type
-constexpr unsigned kSlice = 64;                       // keys of a slice: one thread in the plan, one wave in the exact test
-static_assert(kKeys / kSlice == kThreads, "one slice per thread");
+static_assert(table::kSlices == kThreads, "one slice per thread");
 
 struct Args {
   const unsigned short* x;            // [N][L], bf16 or fp16 bits
@@ -67,11 +68,6 @@ struct Shared {
   double red[kWaves];
   Best wbest[kWaves];
 };
-
-__device__ __forceinline__ unsigned phys(unsigned key) { return key ^ ((key >> 6) & 31u); }
-
-template <bool F16>
-__device__ __forceinline__ double key_value(unsigned key) { return (double)to_f32<F16>(key); }
 
 template <bool F16, bool VEC>
 __global__ __launch_bounds__(kThreads) void solve_quant_rows(Args a) {
@@ -301,41 +297,15 @@ __global__ __launch_bounds__(kThreads) void solve_quant_rows(Args a) {
   }
 }
 
-// the largest key whose value is <= alpha (alpha >= 0): the key of the clamp bound where the bound is a value of the type
-template <bool F16>
-unsigned key_of_bound(float alpha) {
-  auto value = [](unsigned key) {
-    if constexpr (F16) return (float)__builtin_bit_cast(_Float16, (unsigned short)key);
-    else return __builtin_bit_cast(float, key << 16);
-  };
-  unsigned lo = 0u, hi = F16 ? 0x7C00u : 0x7F80u;     // 0 .. +inf
-  while (lo < hi) {
-    const unsigned mid = (lo + hi + 1u) >> 1;
-    if (value(mid) <= alpha) lo = mid; else hi = mid - 1u;
-  }
-  return lo;
-}
-
 template <bool F16, bool VEC>
 int launch(Args a, hipStream_t st) {
-  a.kmax = a.alpha >= 0.f ? key_of_bound<F16>(a.alpha) : kKeys - 1u;
-  const unsigned lds = (a.kmax / kSlice + 1u) * kSlice * 4u;
-  // dynamic LDS above 64 KiB needs the function attribute, once per device
-  static std::atomic<unsigned long long> allowed{0ull};
-  int dev = 0;
-  hipError_t rc = hipGetDevice(&dev);
+  a.kmax = table::top_key<F16>(a.alpha);
+  const hipError_t rc = table::allow_full_table<&solve_quant_rows<F16, VEC>>();
   if (rc != hipSuccess) return (int)rc;
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(allowed.load(std::memory_order_acquire) & bit)) {
-    rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_quant_rows<F16, VEC>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kKeys * 4u));
-    if (rc != hipSuccess) return (int)rc;
-    allowed.fetch_or(bit, std::memory_order_release);
-  }
   // One workgroup a row, N < 2^31 workgroups: the hardware takes them in turn.  (A loop over rows inside the kernel lets the
   // compiler keep every row-invariant mask and bound live across it: 30 to 35 scalar registers spilled, 111 vector
   // registers against 76.)
-  hipLaunchKernelGGL((solve_quant_rows<F16, VEC>), dim3((unsigned)a.N), dim3(kThreads), lds, st, a);
+  hipLaunchKernelGGL((solve_quant_rows<F16, VEC>), dim3((unsigned)a.N), dim3(kThreads), table::table_bytes(a.kmax), st, a);
   return (int)hipGetLastError();
 }
 

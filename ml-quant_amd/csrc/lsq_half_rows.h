@@ -1,7 +1,7 @@
 // Reading bf16 / fp16 rows in GROUPS of 8 elements (byte g of a row's plane words = its elements 8 g .. 8 g + 7), shared by
-// the 16-bit activation quantizers (linear_act_half/lsq_linear_act_half.hip, linear_act_solve/lsq_linear_act_solve.hip):
-// the exact conversion to fp32, the symmetric clamp, the group load on either alignment and the wave sum whose order is
-// the same in every lane.
+// the three 16-bit activation quantizers (linear_act_half/lsq_linear_act_half.hip, linear_act_solve/lsq_linear_act_solve.hip,
+// conv_act_half/lsq_conv_act_half.hip; the last two also through linear_act_solve/lsq_half_table.h): the exact conversion
+// to fp32, the symmetric clamp, the group load on either alignment and the wave sum whose order is the same in every lane.
 #pragma once
 
 #include <hip/hip_runtime.h>

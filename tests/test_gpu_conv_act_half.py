@@ -255,6 +255,40 @@ def test_zero_samples_and_negative_zero(dt, gi):
             assert (status == (0 if scheme in (LS2, LST) else 1)).all()
 
 
+@pytest.mark.parametrize('gi', (2, 8))
+@pytest.mark.parametrize('dt', DTYPES)
+def test_constant_and_fully_clamped_samples(dt, gi):
+    """The table solve where one key holds a whole sample (geometry 3: 2-byte loads, M = 3087; geometry 9: 16-byte loads,
+    M = 2048), ls-2 / ls-T free-running, skip 1 and 3.  Samples of 0.75 without a clamp: every candidate lies in one slice,
+    ls-2 finds v1 = c inside the run and ls-T its extra candidate c / 2.  Samples with |x| >= 2 under the bound 0.5: every
+    element is counted on key(alpha), both signs.  v1 bit for bit and status against lsq_exact and against
+    lsq_linear_act_quant_solve_half on the flat rows; the interior words against the CPU chain."""
+    hip = _hip()
+    c, h, w = C.GEOMS[gi][:3]
+    m = c * h * w
+    dtype = DTYPES[dt]
+    big = detgen.normal(f'convacthalf.big.{gi}', (2, c, h, w), seed=gi, scale=1.0)
+    big = (big + torch.where(big >= 0, 2.0, -2.0)).to(dtype)
+    assert (big.float().abs() >= 2).all()
+    for what, x16, alpha in (('constant', torch.full((2, c, h, w), 0.75, dtype=dtype), -1.0), ('clamped', big, 0.5)):
+        for name, scheme in (('ls-2', LS2), ('ls-T', LST)):
+            for skip in C.SKIPS:
+                planes, scales, status = _quant(x16.to(DEV), gi, scheme, 2, alpha, skip)
+                want_v1, found = C.oracle_rows(C.clamped32(x16.view(2, m), alpha), scheme == LST, skip)
+                lin_planes = torch.zeros((2 * 2 * ((m + 63) // 64),), dtype=torch.int64, device=DEV)
+                lin_scales = torch.empty((2, 2), device=DEV)
+                hip.linear_act_quant_solve_half(x16.to(DEV).view(2, m), scheme, skip, alpha, lin_planes, lin_scales)
+                words, _ = _expected_words(x16, gi, alpha, scales)
+                print(f'{what} {name} {dt} geometry {gi + 1} skip={skip}: v1 {scales[0].tolist()} oracle {want_v1.tolist()} '
+                      f'linear {lin_scales[0].tolist()} status {status.tolist()} found {found.tolist()}')
+                assert torch.equal(scales[0].view(torch.int32), torch.from_numpy(want_v1).view(torch.int32))
+                assert torch.equal(scales[0].view(torch.int32), lin_scales[0].cpu().view(torch.int32))
+                assert torch.equal(status.bool(), torch.from_numpy(found))
+                assert torch.equal(_interior(gi, planes), _interior(gi, words))
+                if what == 'constant':
+                    assert (scales[0] == (0.375 if scheme == LST else 0.75)).all()
+
+
 @pytest.mark.parametrize('dt', DTYPES)
 def test_negative_subnormals(dt):
     """64 negative subnormals -k * (smallest subnormal), k = 1 .. 64, as a sample (64, 1, 1): every bit 0 (a flushed value

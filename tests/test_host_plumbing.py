@@ -3,6 +3,7 @@
 
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -223,3 +224,23 @@ def test_the_shared_conv_core_is_a_prerequisite_of_both_libraries_that_instantia
         out = subprocess.run(['make', '-n', '-W', header, '-W', os.path.basename(header), '-C', os.path.join(csrc, sub)],
                              check=True, capture_output=True, text=True).stdout      # (the Makefiles spell it both ways)
         assert any(' -c ' in line and obj in line for line in out.splitlines()), (sub, out)
+
+
+def test_the_shared_count_table_solve_is_a_prerequisite_of_both_libraries_and_is_written_once():
+    """csrc/linear_act_solve/lsq_half_table.h holds the count table of liblsq_hip_linear_act_solve.so and
+    liblsq_hip_conv_act_half.so (its constants, phys(), the host helpers; solve_v1): `make -n -W <header>` (a query) after a
+    build must want to recompile each one's object, and the pieces both files used to carry -- phys() and key_of_bound -- are
+    defined in exactly one file under csrc/."""
+    csrc = os.path.join(ROOT, 'ml-quant_amd', 'csrc')
+    header = os.path.join(csrc, 'linear_act_solve', 'lsq_half_table.h')
+    assert os.path.exists(header)
+    for sub in ('linear_act_solve', 'conv_act_half'):
+        subprocess.run(['make', '-C', os.path.join(csrc, sub)], check=True, capture_output=True)     # (nothing to do after build())
+        out = subprocess.run(['make', '-n', '-W', header, '-C', os.path.join(csrc, sub)], check=True, capture_output=True,
+                             text=True).stdout
+        lines = [line for line in out.splitlines() if ' -c ' in line]
+        assert len(lines) == 1 and f'lsq_{sub}.hip' in lines[0] and f'{sub}_lsq_{sub}.o' in lines[0], (sub, lines)
+    sources = [os.path.join(d, f) for d, _, files in os.walk(csrc) for f in files if f.endswith(('.h', '.hip'))]
+    for definition in (r'\bunsigned\s+phys\s*\(', r'\bunsigned\s+key_of_bound\s*\('):
+        holders = [os.path.relpath(p, csrc) for p in sources if re.search(definition, open(p).read())]
+        assert holders == [os.path.join('linear_act_solve', 'lsq_half_table.h')], (definition, holders)
