@@ -3,7 +3,10 @@
 #ifndef LSQ_XNOR_CONV_H_
 #define LSQ_XNOR_CONV_H_
 
+#include <type_traits>
+
 #include "lsq_common.h"
+#include "lsq_hip_linear_half.h"       // LSQ_DTYPE_*
 
 namespace lsq {
 
@@ -47,7 +50,31 @@ struct ConvArgs {
   const float* proj_bias;              // [O] or null
   int proj_c, proj_h, proj_w_in, proj_stride;
   int proj_post;                       // 0: the value plays res_pre, 1: res_post
+  // ---- 16-bit epilogue I/O (lsq_xnor_conv2d_half): the final launch of a call reads res_pre / res_post and writes y in
+  // io_dtype (the three fields above keep their float types and are cast in the 16-bit instantiations); the fp32 running
+  // sum of a multi-launch call lives in `sum`, which the launches before the last write as their fp32 y
+  const float* sum;                    // [N][O][Ho][Wo] fp32: the accumulate read of a 16-bit launch (fp32 launches read y)
+  int io_dtype;                        // LSQ_DTYPE_F32 (0, every other entry point) | LSQ_DTYPE_BF16 | LSQ_DTYPE_F16: THIS launch's
 };
+
+// The epilogue's memory accesses in the I/O type T of a kernel instantiation: float (as ever), __bf16 or _Float16.  A 16-bit
+// load widens exactly; a 16-bit store is ONE round-to-nearest-even of the final fp32 value, the conversion Tensor.to(dtype)
+// makes (fp16 overflow -> +-inf, results in the subnormal range stay subnormals).
+template <typename T>
+__device__ __forceinline__ float epi_load(const T* p) {
+  if constexpr (std::is_same<T, __bf16>::value) return __uint_as_float((unsigned)*reinterpret_cast<const unsigned short*>(p) << 16);
+  else return (float)*p;
+}
+template <typename T>
+__device__ __forceinline__ float epi_load_nt(const T* p) {
+  if constexpr (std::is_same<T, __bf16>::value)
+    return __uint_as_float((unsigned)__builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(p)) << 16);
+  else return (float)__builtin_nontemporal_load(p);
+}
+template <typename T>
+__device__ __forceinline__ void epi_store(T* p, float v) {
+  *p = (T)v;
+}
 
 // The projection operand of lsq_xnor_conv2d_proj's kernel: channels a multiple of 64 (the k order of lsq_pointwise.hip, in
 // chunks of 64), at most kProjMaxChannels (32 x (C + 4) floats of LDS next to the weight fragments).

@@ -32,8 +32,11 @@ constexpr int kDefaultOT = 16;
 // set); the chain epilogue is always exact, so only up to here are its units the scale lsq_act_quant would return
 constexpr long long kChainMaxRow = 1ll << 22;
 
-template <int KX, int OT>
+// T: the epilogue's I/O type (lsq_xnor_conv.h, epi_load / epi_store): float, or __bf16 / _Float16 in the final launch of
+// lsq_xnor_conv2d_half, which reads the fp32 sum of the launches before it from a.sum.
+template <int KX, int OT, typename T = float>
 __global__ __launch_bounds__(256) void xnor_conv_kernel(ConvArgs a) {
+  constexpr bool kF32 = std::is_same<T, float>::value;
   // tap sums of this block's OT out-channels for the halo correction: whole-tap, per kernel row and per
   // kernel column (inclusion-exclusion), so that a border pixel pays ~3 LDS reads per channel instead of
   // up to KH*KW global reads -- every wave contains border pixels once rows are narrower than 64
@@ -193,16 +196,20 @@ __global__ __launch_bounds__(256) void xnor_conv_kernel(ConvArgs a) {
   for (int p = 0; p < KX; ++p) xs[p] = a.xscales[(long long)p * a.N + n];
   const int full = a.cg * taps;
   const long long ybase = ((long long)n * a.O + o0) * HoWo + r;
-  float* yp = a.y + ybase;
+  T* yp = reinterpret_cast<T*>(a.y) + ybase;
   // the residual loads are issued together, before the first store: a load consumed right after it is
   // issued costs one memory latency per out-channel.  One residual array in registers (the block adds its
   // shortcut either before or after the ReLU); with both present the second is read in place.
   const bool want_pre = a.final_pass && a.res_pre, want_post = a.final_pass && a.res_post;
-  const float* rsrc = want_pre ? a.res_pre : a.res_post;
+  const T* rsrc = reinterpret_cast<const T*>(want_pre ? a.res_pre : a.res_post);
   float rv[OT];
 #pragma unroll
-  for (int o = 0; o < OT; ++o)
-    rv[o] = (want_pre || want_post) ? rsrc[ybase + (o < o_valid ? (long long)o * HoWo : 0)] : 0.f;
+  for (int o = 0; o < OT; ++o) {
+    // (the fp32 instantiations spelled as they were before T: through epi_load the compiler emitted the same instructions
+    //  with the operands of the residual adds swapped)
+    if constexpr (kF32) rv[o] = (want_pre || want_post) ? rsrc[ybase + (o < o_valid ? (long long)o * HoWo : 0)] : 0.f;
+    else rv[o] = (want_pre || want_post) ? epi_load(rsrc + (ybase + (o < o_valid ? (long long)o * HoWo : 0))) : 0.f;
+  }
 #pragma unroll
   for (int o = 0; o < OT; ++o) {
     if (o < o_valid) {
@@ -212,20 +219,27 @@ __global__ __launch_bounds__(256) void xnor_conv_kernel(ConvArgs a) {
       float v = xs[0] * (float)(fc - (acc[0][o] << 1));
 #pragma unroll
       for (int p = 1; p < KX; ++p) v = fmaf(xs[p], (float)(fc - (acc[p][o] << 1)), v);
-      const float base = a.accumulate ? yp[(long long)o * HoWo] : (a.bias ? a.bias[o0 + o] : 0.f);
+      float base;                // (the accumulate read is fp32 in every instantiation: y itself, or the sum beside a 16-bit y)
+      if constexpr (kF32) base = a.accumulate ? yp[(long long)o * HoWo] : (a.bias ? a.bias[o0 + o] : 0.f);
+      else base = a.accumulate ? a.sum[ybase + (long long)o * HoWo] : (a.bias ? a.bias[o0 + o] : 0.f);
       float out = fmaf(v, a.wscale[o0 + o], base);
       if (a.final_pass) {        // fused block epilogue (non-linearity and shortcut adds of resnet.py:182-190)
         if (want_pre) out += rv[o];
         if (a.relu == LSQ_ACT_RELU) out = fmaxf(out, 0.f);
         else if (a.relu >= LSQ_ACT_PRELU) out = out > 0.f ? out : a.slope[a.relu == LSQ_ACT_PRELU ? 0 : o0 + o] * out;
-        if (want_post) out += want_pre ? a.res_post[ybase + (long long)o * HoWo] : rv[o];
+        if constexpr (kF32) {
+          if (want_post) out += want_pre ? a.res_post[ybase + (long long)o * HoWo] : rv[o];
+        } else {
+          if (want_post) out += want_pre ? epi_load(reinterpret_cast<const T*>(a.res_post) + (ybase + (long long)o * HoWo)) : rv[o];
+        }
       }
-      yp[(long long)o * HoWo] = out;
+      if constexpr (kF32) yp[(long long)o * HoWo] = out;
+      else epi_store(yp + (long long)o * HoWo, out);
     }
   }
 }
 
-template <int KX>
+template <int KX, typename T = float>
 int launch_kx(ConvArgs a, int groups, hipStream_t st) {
   const long long total = (long long)a.N * a.Ho * a.Wo;
   // out-channels per lane: the weight plane is padded to 16 per group; 32 needs og_pad % 32 == 0
@@ -239,9 +253,9 @@ int launch_kx(ConvArgs a, int groups, hipStream_t st) {
 #endif
   a.tiles_per_group = a.og_pad / ot;
   dim3 grid((unsigned)((total + 255) / 256), (unsigned)(groups * a.tiles_per_group));
-  if (ot == 32) hipLaunchKernelGGL((xnor_conv_kernel<KX, 32>), grid, dim3(256), 0, st, a);
-  else if (ot == 8) hipLaunchKernelGGL((xnor_conv_kernel<KX, 8>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((xnor_conv_kernel<KX, 16>), grid, dim3(256), 0, st, a);
+  if (ot == 32) hipLaunchKernelGGL((xnor_conv_kernel<KX, 32, T>), grid, dim3(256), 0, st, a);
+  else if (ot == 8) hipLaunchKernelGGL((xnor_conv_kernel<KX, 8, T>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((xnor_conv_kernel<KX, 16, T>), grid, dim3(256), 0, st, a);
   return (int)hipGetLastError();
 }
 
@@ -259,7 +273,9 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
                             const lsq_conv_geom* g, int relu, const float* act_slope, const float* res_pre,
                             const float* res_post, float* y, void* stream,
                             const int64_t* x_units, float x_alpha, const lsq_next_ls1* next, const lsq_proj* proj = nullptr,
-                            bool with_proj = false) {
+                            bool with_proj = false, int io_dtype = LSQ_DTYPE_F32, void* workspace = nullptr,
+                            size_t workspace_bytes = 0) {
+  // io_dtype != LSQ_DTYPE_F32 (lsq_xnor_conv2d_half): y, res_pre and res_post point at 16-bit elements of that type
   if (with_proj && (!proj || !proj->x || !proj->w)) return LSQ_E_NULL;
   if (!xplanes || (!xscales && !x_units) || !wbits || !wsum || !wscales || !y) return LSQ_E_NULL;
   if (int e = check_geom(g)) return e;
@@ -289,7 +305,8 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
   a.slope = act_slope;
   a.res_pre = res_pre;
   a.res_post = res_post;
-  a.res_stream = 2ll * 4 * (long long)g->N * g->O * Ho * Wo > kInfinityCacheBytes;
+  // (the bytes of a residual plus the output, each in its own type)
+  a.res_stream = 2ll * (io_dtype == LSQ_DTYPE_F32 ? 4 : 2) * (long long)g->N * g->O * Ho * Wo > kInfinityCacheBytes;
   const bool chained = x_units != nullptr || next != nullptr;
   if (chained) {
     // chained 1-bit layers run on the integer-MFMA kernel only (3x3, C in {64, 128, 256, 512}); one activation plane
@@ -340,6 +357,17 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
     a.proj_post = proj->post ? 1 : 0;
     a.res_stream = 0;              // (no residual tensor is streamed: a res_post tensor beside a res_pre projection is read in place)
   }
+  const bool half_io = io_dtype != LSQ_DTYPE_F32;
+  if (half_io) {
+    // 16-bit y and residuals: only the LAST launch reads and writes them; the launches before it are the fp32 kernels on an
+    // fp32 workspace that the last one reads as its running sum.  Refusals here, before any launch.
+    if (io_dtype != LSQ_DTYPE_BF16 && io_dtype != LSQ_DTYPE_F16) return LSQ_E_UNSUPPORTED;
+    if (chained || with_proj) return LSQ_E_UNSUPPORTED;
+    if (kw_planes * ((kx + 1) / 2) > 1) {
+      const size_t need = sizeof(float) * (size_t)g->N * (size_t)g->O * (size_t)Ho * (size_t)Wo;
+      if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3) || workspace_bytes < need) return LSQ_E_WORKSPACE;
+    }
+  }
   const long long wplane_words = lsq_weight_plane_words(g);
   const int taps = g->KH * g->KW;
   hipStream_t st = (hipStream_t)stream;
@@ -355,10 +383,19 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
       a.accumulate = first ? 0 : 1;
       a.final_pass = (q == kw_planes - 1 && p0 + np >= kx) ? 1 : 0;
       const int impl = g_force_popcount.load(std::memory_order_relaxed);      // 0: matrix cores (fp4), 1: popcount kernel, 2: matrix cores (int8)
-      a.int8_mfma = impl == 2;
+      a.int8_mfma = impl == 2 && !half_io;      // (a 16-bit call: the fp4 kernel in every launch)
+      if (half_io) {
+        a.io_dtype = a.final_pass ? io_dtype : LSQ_DTYPE_F32;
+        a.y = a.final_pass ? y : static_cast<float*>(workspace);
+        a.sum = static_cast<const float*>(workspace);
+      }
       int e = (impl == 1 && !chained) ? kXnorMfmaNotEligible : xnor_conv_mfma(a, np, g->groups, st);
       if (e == kXnorMfmaNotEligible && chained) return LSQ_E_UNSUPPORTED;
-      if (e == kXnorMfmaNotEligible) e = np == 2 ? launch_kx<2>(a, g->groups, st) : launch_kx<1>(a, g->groups, st);
+      if (e == kXnorMfmaNotEligible) {
+        if (a.io_dtype == LSQ_DTYPE_BF16) e = np == 2 ? launch_kx<2, __bf16>(a, g->groups, st) : launch_kx<1, __bf16>(a, g->groups, st);
+        else if (a.io_dtype == LSQ_DTYPE_F16) e = np == 2 ? launch_kx<2, _Float16>(a, g->groups, st) : launch_kx<1, _Float16>(a, g->groups, st);
+        else e = np == 2 ? launch_kx<2>(a, g->groups, st) : launch_kx<1>(a, g->groups, st);
+      }
       if (e) return e;
       first = false;
     }
@@ -383,6 +420,26 @@ int xnor_conv2d_proj(const uint64_t* xplanes, int kx, const float* xscales, cons
                      void* stream) {
   return xnor_conv2d_impl(xplanes, kx, xscales, wbits, wsum, kw_planes, wscales, bias, g, act, act_slope, res_pre, res_post, y,
                           stream, nullptr, -1.f, nullptr, proj, true);
+}
+
+// lsq_xnor_conv2d_half of liblsq_hip_conv_xnor_half.so (include/lsq_hip_conv_xnor_half.h), which links this library for it:
+// y, res_pre and res_post are 16-bit tensors of `dtype`
+int xnor_conv2d_half(const uint64_t* xplanes, int kx, const float* xscales, const uint64_t* wbits, const int32_t* wsum,
+                     int kw_planes, const float* wscales, const float* bias, const lsq_conv_geom* g, int act,
+                     const float* act_slope, const void* res_pre, const void* res_post, int dtype, void* y, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  // (another dtype -- LSQ_DTYPE_F32 included -- is refused where the checks lsq_xnor_conv2d shares have passed)
+  return xnor_conv2d_impl(xplanes, kx, xscales, wbits, wsum, kw_planes, wscales, bias, g, act, act_slope,
+                          static_cast<const float*>(res_pre), static_cast<const float*>(res_post), static_cast<float*>(y), stream,
+                          nullptr, -1.f, nullptr, nullptr, false, dtype == LSQ_DTYPE_F32 ? -1 : dtype, workspace, workspace_bytes);
+}
+
+// 0 for a call of one launch (or a geometry the call refuses), else the fp32 running sum: 4 N O Ho Wo
+size_t xnor_conv2d_half_workspace_bytes(const lsq_conv_geom* g, int kx, int kw_planes) {
+  if (check_geom(g) || kx < 1 || kx > LSQ_MAX_PLANES || kw_planes < 1 || kw_planes > LSQ_MAX_PLANES) return 0;
+  const int Ho = out_h(g), Wo = out_w(g);
+  if (Ho <= 0 || Wo <= 0 || kw_planes * ((kx + 1) / 2) <= 1) return 0;
+  return sizeof(float) * (size_t)g->N * (size_t)g->O * (size_t)Ho * (size_t)Wo;
 }
 }  // namespace lsq
 

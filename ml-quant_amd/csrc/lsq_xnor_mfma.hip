@@ -66,9 +66,15 @@ constexpr unsigned kM0 = 0x01010101u;
 // lane gathers its pixel's x with 4-byte loads, chunk c + 1 in flight during the MFMAs of chunk c.
 extern __shared__ __attribute__((aligned(16))) float s_pw[];         // PROJ: [32 out-channels][Cp + 4]
 
-template <int KX, int GG, int TAPS, int NWAVES, int WPC, bool CHAIN, bool FP4, bool PROJ = false>
+// T (lsq_xnor_conv2d_half): the type of the residuals read and of the y written, float, __bf16 or _Float16.  Nothing but the
+// epilogue's loads and stores knows it (epi_load / epi_store of lsq_xnor_conv.h): the arithmetic is the fp32 one, rounded once
+// at the store.  A 16-bit instantiation is the LAST launch of its call; the fp32 sum of the launches before it is read from
+// a.sum, not from y.
+template <int KX, int GG, int TAPS, int NWAVES, int WPC, bool CHAIN, bool FP4, bool PROJ = false, typename T = float>
 __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a) {
   static_assert(!PROJ || (FP4 && !CHAIN), "the projection runs in the unchained fp4 kernel only");
+  constexpr bool kF32 = std::is_same<T, float>::value;
+  static_assert(kF32 || (FP4 && !CHAIN && !PROJ), "16-bit epilogue I/O: the unchained fp4 kernel without projection only");
   constexpr int NT = 64 * NWAVES;
   constexpr int FPS = FP4 ? 1 : 2;               // 16-byte weight fragments per (word, tap) step: int8 K = 32 twice, fp4 K = 64 once
   constexpr int NF = TAPS * GG * FPS;            // 16-byte operand fragments per lane
@@ -385,13 +391,13 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
 #pragma unroll
       for (int i = 0; i < 16; ++i) rv[i] = pacc[i] + reinterpret_cast<const float*>(&pbv[i >> 2])[i & 3];
     } else if (want_pre || want_post) {
-      const float* __restrict__ rsrc = want_pre ? a.res_pre : a.res_post;
+      const T* __restrict__ rsrc = reinterpret_cast<const T*>(want_pre ? a.res_pre : a.res_post);
       if (a.res_stream) {           // (uniform) last use of a tensor that does not fit the Infinity Cache next to the output: lsq_xnor_conv.h
 #pragma unroll
-        for (int i = 0; i < 16; ++i) rv[i] = __builtin_nontemporal_load(rsrc + koff(i) + yoff);
+        for (int i = 0; i < 16; ++i) rv[i] = epi_load_nt(rsrc + koff(i) + yoff);
       } else {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) rv[i] = (rsrc + koff(i))[yoff];
+        for (int i = 0; i < 16; ++i) rv[i] = epi_load((rsrc + koff(i)) + yoff);
       }
     } else {
 #pragma unroll
@@ -399,7 +405,7 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
     }
     if (acc_in) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i) basev[i] = (a.y + koff(i))[yoff];
+      for (int i = 0; i < 16; ++i) basev[i] = ((kF32 ? a.y : a.sum) + koff(i))[yoff];
     } else {
 #pragma unroll
       for (int i = 0; i < 16; ++i) basev[i] = s_bias[ob + (i & 3) + 8 * (i >> 2)];
@@ -556,14 +562,14 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
       }
       if (want_post && want_pre) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) outv[i] += (a.res_post + koff(i))[yoff];
+        for (int i = 0; i < 16; ++i) outv[i] += epi_load((reinterpret_cast<const T*>(a.res_post) + koff(i)) + yoff);
       }
 #ifdef LSQ_XNOR_CLOCKS
       asm volatile("" :: "v"(outv[0]), "v"(outv[15]));
       XCLK();
 #endif
 #pragma unroll
-      for (int i = 0; i < 16; ++i) (a.y + koff(i))[yoff] = outv[i];
+      for (int i = 0; i < 16; ++i) epi_store((reinterpret_cast<T*>(a.y) + koff(i)) + yoff, outv[i]);
       if constexpr (CHAIN) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) nqv[i] = outv[i];
@@ -635,7 +641,7 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
 #endif
 }
 
-template <int KX, int GG, bool FP4 = true>
+template <int KX, int GG, bool FP4 = true, typename T = float>
 int launch(const ConvArgs& a, hipStream_t st) {
   // launch shape per channel count: waves per workgroup, workgroups per CU, and WPC = the waves per SIMD the register
   // allocation must allow (__launch_bounds__'s second argument).  The fp4 kernel runs as ONE workgroup of TWELVE waves per CU
@@ -665,7 +671,9 @@ int launch(const ConvArgs& a, hipStream_t st) {
   long long gx = (wgs + n_ot - 1) / n_ot;
   gx = gx < 1 ? 1 : gx;
   if (gx * NWAVES > ntiles) gx = (ntiles + NWAVES - 1) / NWAVES;
-  if constexpr (!FP4) {
+  if constexpr (!std::is_same<T, float>::value) {      // (16-bit I/O: the same launch shape, the plain fp4 kernel)
+    hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, true, false, T>), dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), 0, st, a);
+  } else if constexpr (!FP4) {
     hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, false>), dim3((unsigned)gx, (unsigned)n_ot), dim3(64 * NWAVES), 0, st, a);
   } else {
     if (KX == 1 && (a.xunits || a.nq_planes32))
@@ -701,8 +709,22 @@ int launch_proj(const ConvArgs& a, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+// the final launch of lsq_xnor_conv2d_half: fp4, unchained, no projection (the entry point refuses the rest)
+template <int KX, typename T>
+int launch_gg_half(const ConvArgs& a, hipStream_t st) {
+  switch (a.cg) {
+    case 64: return launch<KX, 1, true, T>(a, st);
+    case 128: return launch<KX, 2, true, T>(a, st);
+    case 256: return launch<KX, 4, true, T>(a, st);
+    case 512: return launch<KX, 8, true, T>(a, st);
+  }
+  return kXnorMfmaNotEligible;
+}
+
 template <int KX>
 int launch_gg(const ConvArgs& a, hipStream_t st) {
+  if (a.io_dtype == LSQ_DTYPE_BF16) return launch_gg_half<KX, __bf16>(a, st);
+  if (a.io_dtype == LSQ_DTYPE_F16) return launch_gg_half<KX, _Float16>(a, st);
   if constexpr (KX == 2) {
     if (a.proj_x) {
       switch (a.cg) {

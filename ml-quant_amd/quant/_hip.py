@@ -642,6 +642,7 @@ conv_half_lib, conv_half_library_path, CONV_HALF_ABI_VERSION = _sublib('conv_hal
 conv_train_lib, conv_train_library_path, CONV_TRAIN_ABI_VERSION = _sublib('conv_train')
 conv_train_half_lib, conv_train_half_library_path, CONV_TRAIN_HALF_ABI_VERSION = _sublib('conv_train_half')
 conv_proj_lib, conv_proj_library_path, CONV_PROJ_ABI_VERSION = _sublib('conv_proj')
+conv_xnor_half_lib, conv_xnor_half_library_path, CONV_XNOR_HALF_ABI_VERSION = _sublib('conv_xnor_half')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1080,6 +1081,70 @@ def signw_conv2d_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscale
                          f'C{C}_H{H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
         check(hl.lsq_signw_conv2d_half(x.data_ptr(), xdt, float(alpha), wbits.data_ptr(), kw, wscales.data_ptr(), ptr(bias),
                                        ctypes.byref(geom), y.data_ptr(), ydt, *_ws_args(ws), stream_ptr(dev)), what)
+    return y
+
+
+# ---- the XNOR convolution with a 16-bit epilogue (include/lsq_hip_conv_xnor_half.h)
+def xnor_conv2d_half(planes: torch.Tensor, k: int, xscales: torch.Tensor, wbits: torch.Tensor, wsum: torch.Tensor,
+                     wscales: torch.Tensor, bias: Optional[torch.Tensor], geom: ConvGeom, dtype: torch.dtype,
+                     relu: bool = False, res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
+                     prelu: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [N, O, Ho, Wo] of ``dtype`` (bf16 / fp16) = act(conv + bias + res_pre) + res_post from the operands of
+    ``xnor_conv2d`` (lsq_xnor_conv2d_half): the residuals are tensors of ``dtype`` and y's shape, read as they are; the fp32
+    result is rounded once -- bit for bit ``xnor_conv2d`` on ``res.float()`` followed by ``.to(dtype)``.  The fp32 running sum
+    of a call of more than one launch (kw * ceil(k / 2) > 1) lives in a workspace cached per (device, stream) like the
+    solver's (rewritten by every call; kernels of one stream run in order)."""
+    what = 'lsq_xnor_conv2d_half'
+    k = int(k)
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f'{what}: dtype must be torch.bfloat16 or torch.float16, got {dtype}')
+    res = {name: t for name, t in (('res_pre', res_pre), ('res_post', res_post)) if t is not None}
+    wrong = [name for name, t in res.items() if t.dtype != dtype]
+    if wrong:
+        raise TypeError(f'{what}: {", ".join(wrong)} must be {dtype} tensors')
+    fp32 = {'xscales': xscales, 'wscales': wscales}
+    if bias is not None:
+        fp32['bias'] = bias
+    if prelu is not None:
+        fp32['prelu'] = prelu
+    ho, wo = out_hw(geom)
+    shape = (geom.N, geom.O, ho, wo)
+
+    def problem():
+        if k < 1 or wscales.dim() != 2 or wscales.shape[0] < 1 or min(shape) < 1:
+            return f'bad sizes: k={k}, wscales of shape {tuple(wscales.shape)}, output {shape}'
+        if tuple(xscales.shape) != (k, geom.N) or planes.numel() < k * geom.N * geom.groups * (
+                (geom.C // max(geom.groups, 1) + 63) // 64) * (geom.H + 2 * geom.pad_h) * (geom.W + 2 * geom.pad_w):
+            return 'activation planes / scales and (k, geometry) do not match'
+        if wscales.shape[1] != geom.O or wbits.numel() < wscales.shape[0] * _signw_plane_words(geom) \
+                or tuple(wsum.shape) != (wscales.shape[0], geom.O, geom.KH * geom.KW) \
+                or (bias is not None and tuple(bias.shape) != (geom.O,)):
+            return 'weight planes / sums / scales / bias and (kw, geometry) do not match'
+        if prelu is not None and (relu or prelu.numel() not in (1, geom.O)):
+            return f'prelu of {prelu.numel()} slopes on {geom.O} channels' + (' together with relu' if relu else '')
+        for name, t in res.items():
+            if tuple(t.shape) != shape:
+                return f'{name} of shape {tuple(t.shape)} must have the shape of y, {shape}'
+
+    _check_operands(what, fp32, {'planes': planes, 'wbits': wbits}, {'wsum': wsum}, half=list(res.values()), problem=problem)
+    act, slope = _act(relu, None if prelu is None else prelu.detach(), geom.O)
+    dev, kw = planes.device, wscales.shape[0]
+    hl = conv_xnor_half_lib()
+    lib()                                           # (liblsq_hip_conv_xnor_half.so links liblsq_hip.so: the same loaded object)
+    need = int(hl.lsq_xnor_conv2d_half_workspace_bytes(ctypes.byref(geom), k, kw))
+    ws = _stream_buffer('conv_xnor_half', need, dev) if need else None
+    y = torch.empty(shape, dtype=dtype, device=dev)
+    m = geom.C * geom.H * geom.W
+    launches = kw * ((k + 1) // 2)
+    macs = y.numel() * (geom.C // geom.groups) * geom.KH * geom.KW * k * kw
+    # algorithmic bytes: planes read + 16-bit output written + every 16-bit residual read (+ the fp32 sum, written and read
+    # back once per launch before the last)
+    nbytes = geom.N * k * m // 8 + 2 * y.numel() * (1 + len(res)) + 8 * y.numel() * (launches - 1)
+    with _on(y), (_Timed(what, nbytes, macs, f'C{geom.C}_H{geom.H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
+        check(hl.lsq_xnor_conv2d_half(planes.data_ptr(), k, xscales.data_ptr(), wbits.data_ptr(), wsum.data_ptr(), kw,
+                                      wscales.data_ptr(), ptr(bias), ctypes.byref(geom), act, ptr(slope), ptr(res_pre),
+                                      ptr(res_post), LINEAR_HALF_DTYPES[dtype], y.data_ptr(), *_ws_args(ws), stream_ptr(dev)),
+              what)
     return y
 
 

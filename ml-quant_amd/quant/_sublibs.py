@@ -129,6 +129,9 @@ SUBLIBS = (
         'lsq_signw_conv2d_dgrad_half': (i32, [vp, i32, vp, i32, vp, vp, vp, i32, vp, f32, vp, i32, vp, sz, vp])}),
     _entry('conv_proj', '|lsq_xnor_conv2d_proj[a-z0-9_]*', {
         'lsq_xnor_conv2d_proj': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, ctypes.POINTER(Proj), vp, vp])}),
+    _entry('conv_xnor_half', '|lsq_xnor_conv2d_half[a-z0-9_]*', {
+        'lsq_xnor_conv2d_half_workspace_bytes': (sz, [gp, i32, i32]),
+        'lsq_xnor_conv2d_half': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, i32, vp, vp, sz, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

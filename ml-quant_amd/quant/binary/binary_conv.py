@@ -30,6 +30,9 @@ Dispatch of ``forward``:
   * with ``hip_train_half`` set (class attribute, False by default): a bf16 / fp16 CUDA tensor in ``train()`` mode, binary fp32
     weights, autocast off or set to the input's own type -> the 16-bit step of ``quant.binary.hip_train``:
     lsq_act_quant_half / lsq_signw_conv2d_half forward, one lsq_signw_conv2d_dgrad_half for the input gradient;
+  * with ``xnor_half`` set on top of ``act_half`` / ``hip_train_half`` (class attribute, False by default): the XNOR
+    convolution of a 16-bit input is lsq_xnor_conv2d_half (liblsq_hip_conv_xnor_half.so), which writes the input's type itself
+    -- the same bits, no fp32 y --, and ``fused_forward`` hands it non-linearity and 16-bit residuals (DESIGN 4.26);
   * anything else (CPU tensors, grouped / dilated training convolutions, 16-bit inputs with binary activations without
     ``act_half`` or with ``fp`` activations without ``fp_half``, 16-bit weights, an autocast of another type) -> the torch
     formulation in ``quant.binary``.
@@ -107,6 +110,13 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: A switch of its own, independent of ``act_half`` / ``fp_half``.  False: the torch formulation, the default whatever the
     #: measurement says in the change that adds it
     hip_train_half = False
+
+    #: with ``act_half`` (eval) or ``hip_train_half`` (train): the XNOR convolution of a bf16 / fp16 input writes its result in
+    #: the input's type itself (lsq_xnor_conv2d_half: no fp32 y, no ``.to()`` pass -- the same bits), and ``fused_forward`` on
+    #: such an input hands ``relu`` / ``prelu`` and 16-bit residuals to that one launch, which rounds once.  A switch of its
+    #: own; False: lsq_xnor_conv2d + ``.to()`` and the composition in torch, the default whatever the measurement says in the
+    #: change that adds it
+    xnor_half = False
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
@@ -215,6 +225,18 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         On the HIP path the eval-mode batch norm is folded into the quantizer's read and the non-linearity /
         shortcut additions into the convolution's epilogue, so none of them is a separate pass over HBM;
         elsewhere it is the plain composition of the modules."""
+        xin = None
+        if self.xnor_half and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and self.x_quant != 'fp':
+            # a 16-bit input with ``xnor_half``: the batch norm in torch in front of the quantizer (lsq_act_quant_half folds
+            # none), then non-linearity and 16-bit residuals in the epilogue of lsq_xnor_conv2d_half -- one launch, one
+            # rounding.  Residuals of another type or shape take the composition below.
+            if isinstance(res_pre, ProjectionShortcut):
+                res_pre = res_pre.tensor()
+            if isinstance(res_post, ProjectionShortcut):
+                res_post = res_post.tensor()
+            xin = x if pre_bn is None else pre_bn(x)
+            if self._wants_hip(xin) and self._half_epilogue_fits(xin, res_pre, res_post, prelu):
+                return self._forward_hip(xin, None, relu, res_pre, res_post, prelu, None, res_ready)
         if (x.dtype == torch.float32 and self._wants_hip(x)
                 and (pre_bn is None or (not pre_bn.training and pre_bn.track_running_stats))):
             # next_q = (batch norm or None, QuantConv2d) that will consume the result: with 1-bit activations on both
@@ -228,7 +250,7 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             res_post = res_post.tensor()
         if res_ready is not None:
             torch.cuda.current_stream(x.device).wait_event(res_ready)
-        y = self(x if pre_bn is None else pre_bn(x))
+        y = self(xin if xin is not None else (x if pre_bn is None else pre_bn(x)))
         if res_pre is not None:
             y = y + res_pre
         if relu:
@@ -236,6 +258,19 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         if prelu is not None:
             y = F.prelu(y, prelu)
         return y if res_post is None else y + res_post
+
+    def _half_epilogue_fits(self, x: torch.Tensor, res_pre, res_post, prelu) -> bool:
+        """Whether lsq_xnor_conv2d_half's epilogue takes these operands: residuals that are CUDA tensors of the input's type
+        and the output's shape, PReLU slopes in fp32 (1 or one per out-channel)."""
+        from quant import _hip
+        if x.dtype not in (torch.bfloat16, torch.float16) or x.dim() != 4:
+            return False
+        shape = (x.shape[0], self.out_channels) + tuple(_hip.out_hw(self._geom_of(x, _hip)))
+        for r in (res_pre, res_post):
+            if r is not None and not (isinstance(r, torch.Tensor) and r.is_cuda and r.device == x.device and r.dtype == x.dtype
+                                      and tuple(r.shape) == shape):
+                return False
+        return prelu is None or (prelu.is_cuda and prelu.dtype == torch.float32 and prelu.numel() in (1, self.out_channels))
 
     def _folded_bn(self, bn: nn.BatchNorm2d):
         """(scale, shift) with bn(x) = x * scale + shift in eval mode; cached on the BN's buffer versions."""
@@ -325,14 +360,15 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             # a 16-bit input with fp activations (fp_half): the samples as they are against the sign planes, the clamp bound as
             # Tensor.clamp would round it into their type; the kernel rounds its fp32 result once into the input's type
             return _hip.signw_conv2d_half(x.contiguous(), self._alpha_in(x.dtype), wbits, wscales, bias, geom)
-        y = torch.empty((n, self.out_channels, ho, wo), dtype=torch.float32, device=x.device)
+        half_out = self.xnor_half and x.dtype != torch.float32 and self.x_quant != 'fp'      # (lsq_xnor_conv2d_half allocates its y)
+        y = None if half_out else torch.empty((n, self.out_channels, ho, wo), dtype=torch.float32, device=x.device)
         def join():                      # residual operands from a side stream: in front of the convolution, behind the quantizer
             if res_ready is not None:
                 torch.cuda.current_stream(x.device).wait_event(res_ready)
         if x.dtype != torch.float32:
             # a 16-bit input (act_half / fp_half): the samples are read as they are (or cast: the comparator), the clamp bound
-            # as Tensor.clamp would round it into their type; the fp32 result is rounded once.  No folded batch norm, no fused
-            # epilogue (fused_forward composes them in torch), no chaining.
+            # as Tensor.clamp would round it into their type; the fp32 result is rounded once.  No folded batch norm, no
+            # chaining; a fused epilogue only with xnor_half (elsewhere fused_forward composes it in torch).
             x16 = x.contiguous()
             if self.x_quant == 'fp':          # (fp_half_kernel = False: the cast route, the comparator of DESIGN 4.19)
                 _hip.signw_conv2d(x16.float(), self._alpha_in(x.dtype), wbits, wscales, bias, geom, y, wprep=wprep)
@@ -340,8 +376,14 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             k = self.x_approximate.n_planes
             planes, scales = self._act_planes(x16 if self.act_half_kernel else x16.float(), geom, k, _hip,
                                               (geom.pad_h, geom.pad_w, self.groups, x.dtype), alpha=self._alpha_in(x.dtype))
-            _hip.xnor_conv2d(planes, k, scales, wbits, wsum, wscales, bias, geom, y)
             self.last_act_scales = scales
+            if half_out:
+                # xnor_half: the 16-bit result straight from the convolution's epilogue, with whatever fused_forward handed
+                # down (a plain forward hands nothing) -- the bits of the two lines below
+                join()
+                return _hip.xnor_conv2d_half(planes, k, scales, wbits, wsum, wscales, bias, geom, x.dtype, relu, res_pre,
+                                             res_post, prelu)
+            _hip.xnor_conv2d(planes, k, scales, wbits, wsum, wscales, bias, geom, y)
             return y.to(x.dtype)
         if self.x_quant == 'fp':
             join()

@@ -257,9 +257,12 @@ class _QuantConv2dStepHalf(torch.autograd.Function):
             else:
                 planes = step_planes(conv, geom, k, x.device, _hip, (geom.pad_h, geom.pad_w, x.dtype))
             xscales = step_act_quant(conv, x.detach(), geom, planes, _hip, alpha)
-            y32 = torch.empty((n, conv.out_channels) + tuple(_hip.out_hw(geom)), dtype=torch.float32, device=x.device)
-            _hip.xnor_conv2d(planes, k, xscales, wbits, wsum, wscales, b, geom, y32)
-            y = y32.to(x.dtype)                         # one rounding of the fp32 result
+            if conv.xnor_half:                          # the rounding in the convolution's epilogue: the same bits
+                y = _hip.xnor_conv2d_half(planes, k, xscales, wbits, wsum, wscales, b, geom, x.dtype)
+            else:
+                y32 = torch.empty((n, conv.out_channels) + tuple(_hip.out_hw(geom)), dtype=torch.float32, device=x.device)
+                _hip.xnor_conv2d(planes, k, xscales, wbits, wsum, wscales, b, geom, y32)
+                y = y32.to(x.dtype)                     # one rounding of the fp32 result
             conv.last_act_scales = xscales
         ctx.conv, ctx.geom, ctx.alpha = conv, geom, alpha
         ctx.has_bias = bias is not None
