@@ -643,6 +643,7 @@ conv_train_lib, conv_train_library_path, CONV_TRAIN_ABI_VERSION = _sublib('conv_
 conv_train_half_lib, conv_train_half_library_path, CONV_TRAIN_HALF_ABI_VERSION = _sublib('conv_train_half')
 conv_proj_lib, conv_proj_library_path, CONV_PROJ_ABI_VERSION = _sublib('conv_proj')
 conv_xnor_half_lib, conv_xnor_half_library_path, CONV_XNOR_HALF_ABI_VERSION = _sublib('conv_xnor_half')
+train_half_lib, train_half_library_path, TRAIN_HALF_ABI_VERSION = _sublib('train_half')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1263,6 +1264,42 @@ def signw_conv2d_dgrad_half(gy: torch.Tensor, wbits: torch.Tensor, wscales: torc
                                              wscales.data_ptr(), ctypes.byref(geom), ptr(x), kx, ptr(xscales), float(alpha),
                                              gx.data_ptr(), LINEAR_HALF_DTYPES[out_dtype], *_ws_args(ws), stream_ptr(dev)), what)
     return gx
+
+
+# ---- the convolution's 16-bit weight / bias gradient (include/lsq_hip_train_half.h)
+def wgrad_half(planes: torch.Tensor, kx: int, xscales: torch.Tensor, gy: torch.Tensor, geom: ConvGeom, bias: bool = False):
+    """(grad_wq [O, C, KH, KW] fp32, grad_b [O] fp32 or None) of the 16-bit train step in one call (lsq_train_wgrad_half):
+    ``wgrad`` for the bf16 / fp16 output gradient ``gy`` [N, O, Ho, Wo] read as it is (contiguous, any 2-byte-aligned data
+    pointer) -- x_q = sum_p xscales[p][n] (2 bit_p - 1) from the activation planes ``planes`` of ``geom`` and the fp32 scales
+    ``xscales`` [kx, N] -- and with ``bias`` the sum of gy over (n, ho, wo) from the same pass.  The split-K partial sums live
+    in a workspace cached per (device, stream) like the solver's (any content; kernels of one stream run in order)."""
+    what = 'lsq_train_wgrad_half'
+    kx = int(kx)
+    _check_half(what, 'gy', gy)
+    _check_dtypes(what, {'xscales': xscales}, {'planes': planes})
+
+    def problem():
+        if gy.dim() != 4 or gy.numel() == 0 or not 1 <= kx <= MAX_PLANES:
+            return f'bad sizes: gy of shape {tuple(gy.shape)}, kx={kx}'
+        if not _geom_matches_gy(geom, gy):
+            return f'the geometry and gy of shape {tuple(gy.shape)} do not match'
+        if tuple(xscales.shape) != (kx, geom.N) or planes.numel() < kx * geom.N * geom.groups * (
+                (geom.C // geom.groups + 63) // 64) * (geom.H + 2 * geom.pad_h) * (geom.W + 2 * geom.pad_w):
+            return 'activation planes / scales and (kx, geometry) do not match'
+
+    _check_placement(what, [gy, xscales, planes], problem)
+    dev = gy.device
+    tl = train_half_lib()
+    need = int(tl.lsq_train_wgrad_half_workspace_bytes(ctypes.byref(geom), kx, int(bool(bias))))
+    ws = _stream_buffer('wgrad_half', need, dev) if need else None
+    gwq = torch.empty((geom.O, geom.C, geom.KH, geom.KW), dtype=torch.float32, device=dev)
+    gb = torch.empty((geom.O,), dtype=torch.float32, device=dev) if bias else None
+    with _on(gy), (_Timed(what, 2 * gy.numel() + 8 * kx * act_plane_words(geom) + 4 * gwq.numel() + (4 * geom.O if bias else 0),
+                          2 * gy.numel() * geom.C * geom.KH * geom.KW, f'C{geom.C}_H{geom.H}_s{geom.stride_h}')
+                   if _timing is not None else _UNTIMED):
+        check(tl.lsq_train_wgrad_half(planes.data_ptr(), kx, xscales.data_ptr(), gy.data_ptr(), LINEAR_HALF_DTYPES[gy.dtype],
+                                      ctypes.byref(geom), gwq.data_ptr(), ptr(gb), *_ws_args(ws), stream_ptr(dev)), what)
+    return gwq, gb
 
 
 def xnor_impl(mode) -> int:

@@ -132,6 +132,9 @@ SUBLIBS = (
     _entry('conv_xnor_half', '|lsq_xnor_conv2d_half[a-z0-9_]*', {
         'lsq_xnor_conv2d_half_workspace_bytes': (sz, [gp, i32, i32]),
         'lsq_xnor_conv2d_half': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, i32, vp, vp, sz, vp])}),
+    _entry('train_half', '|lsq_train_wgrad_half[a-z0-9_]*', {
+        'lsq_train_wgrad_half_workspace_bytes': (sz, [gp, i32, i32]),
+        'lsq_train_wgrad_half': (i32, [vp, i32, vp, vp, i32, gp, vp, vp, vp, sz, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

@@ -40,7 +40,10 @@ backward  grad_x is ONE ``lsq_signw_conv2d_dgrad_half`` (liblsq_hip_conv_train_h
           forward's own weight planes, the straight-through estimator against the 16-bit x in the kernel's epilogue, a 16-bit
           grad_x -- bit for bit ``lsq_ste_backward(x.float(), lsq_signw_conv2d_dgrad(gy.float())).to(dtype)``.  There is no
           other route for a 16-bit input, so ``DGRAD_KERNEL`` does not matter here; grad_w and grad_b are computed in fp32
-          from one ``gy.float()`` as in the fp32 step.
+          from one ``gy.float()`` as in the fp32 step.  With ``WGRAD_HALF_KERNEL`` (False by default) and binary activations
+          in lsq_train_wgrad's geometry they are ONE ``lsq_train_wgrad_half`` (liblsq_hip_train_half.so) instead:
+          the 16-bit grad_y as it is against the step's own sign planes, grad_b from the same pass -- no ``gy.float()``, no
+          ``x.float()``, no ``lsq_quant_values``.
 """
 
 from typing import List, Optional
@@ -60,6 +63,11 @@ WGRAD_KERNEL = False
 # plane over re-packed planes, stride 2 by zero insertion (False).  Off by default: the landing rule of WGRAD_KERNEL (DESIGN
 # 4.20 holds what was measured).
 DGRAD_KERNEL = False
+
+# the 16-bit step (``hip_train_half``) with binary activations: grad_wq and grad_b from ONE lsq_train_wgrad_half
+# (liblsq_hip_train_half.so) that reads the 16-bit grad_y as it is and the step's own sign planes (True), or the
+# fp32 lines behind gy.float() (False).  A switch of its own, off by default: the landing rule of WGRAD_KERNEL.
+WGRAD_HALF_KERNEL = False
 
 
 def _wgrad_geometry(conv) -> bool:
@@ -251,7 +259,7 @@ class _QuantConv2dStepHalf(torch.autograd.Function):
             xscales = None
         else:
             k = conv.x_approximate.n_planes
-            keep_planes = WGRAD_KERNEL and ctx.needs_input_grad[1] and _wgrad_geometry(conv)
+            keep_planes = (WGRAD_KERNEL or WGRAD_HALF_KERNEL) and ctx.needs_input_grad[1] and _wgrad_geometry(conv)
             if keep_planes:
                 planes = zero_planes(geom, k, x.device, _hip)
             else:
@@ -266,6 +274,7 @@ class _QuantConv2dStepHalf(torch.autograd.Function):
             conv.last_act_scales = xscales
         ctx.conv, ctx.geom, ctx.alpha = conv, geom, alpha
         ctx.has_bias = bias is not None
+        ctx.wgrad_half = bool(WGRAD_HALF_KERNEL and keep_planes)      # (the switch as the forward saw it: it kept the planes)
         empty = x.new_empty(0, dtype=torch.int64)
         ctx.save_for_backward(x, weight, wscales, xscales if xscales is not None else wscales.new_empty(0),
                               planes if keep_planes else empty, wbits if ctx.needs_input_grad[0] else empty)
@@ -283,7 +292,12 @@ class _QuantConv2dStepHalf(torch.autograd.Function):
         gx = gw = gb = None
         if need_x:
             gx = _hip.signw_conv2d_dgrad_half(gy, wbits, wscales, geom, x, xscales, alpha)
-        if need_w or need_b:
+        if need_w and ctx.wgrad_half:
+            # grad_wq, and grad_b with it, from the 16-bit grad_y as it is: no gy.float(), no x.float(), no lsq_quant_values
+            with torch.autocast('cuda', enabled=False):
+                gwq, gb = _hip.wgrad_half(planes, xscales.shape[0], xscales, gy, geom, bias=need_b)
+                gw = _hip.ste_backward(weight.detach(), gwq, wscales, -1.0)
+        elif need_w or need_b:
             with torch.autocast('cuda', enabled=False):
                 gy32 = gy.float()
                 if need_b:
