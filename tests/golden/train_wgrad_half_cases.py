@@ -1,8 +1,10 @@
 """The cases of lsq_train_wgrad_half (include/lsq_hip_train_half.h) as data: the geometries of
-tests/test_gpu_train_wgrad_half.py, each the smallest shape at which one mechanism of csrc/train_half/lsq_wgrad_half.hip can go
-wrong, with the host-side arithmetic of that file's plan() (k-steps, chunks, tiles, the K split, the workspace), a packer of
-activation planes and the fp64 closed form.  tests/test_train_wgrad_half_host.py holds the table to what it says.  Plain Python
-on the CPU; nothing here touches a GPU."""
+tests/test_gpu_train_wgrad_half.py, each the smallest shape at which one mechanism of csrc/train_half/lsq_wgrad_half.hip or of
+csrc/train/lsq_wgrad_core.h (which it shares with lsq_train_wgrad, csrc/train/lsq_wgrad.hip) can go wrong, with the host-side
+arithmetic of the two entries -- each file's count of chunks, lsq_wgrad_core.h's tile_plan() (tiles, the K split) and the
+workspace -- restated independently (plan, plan_fp32), the geometries both entries refuse, a packer of activation planes and the
+fp64 closed form.  tests/test_train_wgrad_half_host.py and tests/test_wgrad_core_host.py hold the table to what it says.  Plain
+Python on the CPU; nothing here touches a GPU."""
 
 import collections
 
@@ -47,7 +49,7 @@ PAIRS = [(c, t) for c in CASES for t in DTYPES]
 
 BOUND = 2e-6          # |g - g64| <= BOUND * sum |gy| |x_q| per element (tests/test_gpu_wgrad.py), |gb - gb64| <= BOUND * sum |gy|
 
-K_STEP, CHUNK_STEPS, TILE, TAP_TILE, TARGET_GROUPS = 16, 4, 64, 9, 512       # csrc/train_half/lsq_wgrad_half.hip
+K_STEP, CHUNK_STEPS, TILE, TAP_TILE, TARGET_GROUPS = 16, 4, 64, 9, 512       # csrc/train/lsq_wgrad_core.h
 
 
 def pair_id(p) -> str:
@@ -67,7 +69,8 @@ Plan = collections.namedtuple('Plan', 'howo sps ksteps chunks TT ntc tiles S chu
 
 def plan(c: Case) -> Plan:
     """plan() of csrc/train_half/lsq_wgrad_half.hip: a sample's positions padded to ``sps`` k-steps of 16, chunks of four
-    k-steps, tiles of 64 out-channels x one channel word x TT taps, S slices of whole chunks (about TARGET_GROUPS workgroups)."""
+    k-steps; then tile_plan() of csrc/train/lsq_wgrad_core.h: tiles of 64 out-channels x one channel word x TT taps, S slices of
+    whole chunks (about TARGET_GROUPS workgroups)."""
     ho, wo = out_hw(c)
     howo = ho * wo
     sps = -(-howo // K_STEP)
@@ -88,6 +91,53 @@ def workspace_bytes(c: Case, with_bias: bool) -> int:
     """The stated rule: nothing for one slice; S slabs, and with the bias S rows of bias partials behind them."""
     p = plan(c)
     return 0 if p.S == 1 else 4 * p.S * (p.slab_floats + (p.bias_floats if with_bias else 0))
+
+
+PlanFp32 = collections.namedtuple('PlanFp32', 'howo chunks TT ntc tiles S chunks_per_split slab_floats workspace_bytes')
+
+
+def plan_fp32(c: Case) -> PlanFp32:
+    """lsq_train_wgrad (csrc/train/lsq_wgrad.hip): chunks are runs of 64 of the N Ho Wo positions, across samples; tiles and
+    slices by the same rule as ``plan``; S slabs of workspace where there is more than one slice."""
+    ho, wo = out_hw(c)
+    chunks = -(-(c.N * ho * wo) // (K_STEP * CHUNK_STEPS))
+    kk = c.k[0] * c.k[1]
+    tt = 1 if kk == 1 else TAP_TILE
+    ntc = -(-kk // tt)
+    tiles = (-(-c.O // TILE)) * (-(-c.C // 64)) * ntc
+    s = max(1, min(-(-TARGET_GROUPS // tiles), chunks))
+    cps = -(-chunks // s)
+    s = -(-chunks // cps)
+    slab = tiles * 4 * tt * 16 * 64
+    return PlanFp32(ho * wo, chunks, tt, ntc, tiles, s, cps, slab, 0 if s == 1 else 4 * s * slab)
+
+
+E_NULL, E_SHAPE, E_SCHEME, E_WORKSPACE, E_UNSUPPORTED = -1, -2, -3, -5, -6          # LSQ_E_* of include/lsq_hip.h
+#: Geometries that lsq_train_wgrad and lsq_train_wgrad_half refuse, and the code of both: make_geom's arguments that differ from
+#: REFUSAL_BASE.  The union of the lists of tests/test_wgrad_cabi.py and tests/test_train_wgrad_half_host.py.
+REFUSAL_BASE = dict(n=4, c=64, h=8, w=8, o=32, kh=3, kw=3, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1)
+REFUSED = (
+    (dict(n=0), E_SHAPE),
+    (dict(o=0), E_SHAPE),
+    (dict(c=0), E_SHAPE),
+    (dict(h=1, w=1, padding=(0, 0)), E_SHAPE),                    # kernel larger than the input
+    (dict(h=1, kh=5), E_SHAPE),
+    (dict(padding=(-1, 1)), E_SHAPE),
+    (dict(stride=(0, 0)), E_SHAPE),
+    (dict(o=30, groups=4), E_SHAPE),                              # O not divisible by groups
+    (dict(groups=2), E_UNSUPPORTED),
+    (dict(dilation=(2, 2)), E_UNSUPPORTED),
+    (dict(dilation=(2, 1)), E_UNSUPPORTED),
+    (dict(stride=(3, 3)), E_UNSUPPORTED),
+    (dict(stride=(1, 2)), E_UNSUPPORTED),                         # unequal strides
+    (dict(padding=(3, 1)), E_UNSUPPORTED),                        # pad > k - 1
+    (dict(padding=(1, 3)), E_UNSUPPORTED),
+    (dict(kh=9, kw=9, h=12, w=12), E_UNSUPPORTED),                # kernel > 8
+    (dict(kh=9, h=16), E_UNSUPPORTED),
+    (dict(o=65536), E_UNSUPPORTED),
+    (dict(c=65536), E_UNSUPPORTED),
+    (dict(n=1 << 20, h=64, w=64), E_UNSUPPORTED),                 # N Ho Wo >= 2^31
+)
 
 
 def pack_planes(bits: torch.Tensor, pad) -> torch.Tensor:
