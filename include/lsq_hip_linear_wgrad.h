@@ -1,7 +1,8 @@
 /*
  * lsq_hip_linear_wgrad.h -- C ABI of the weight-gradient kernel of the linear layer (liblsq_hip_linear_wgrad.so), a library
- * of its own beside liblsq_hip.so, liblsq_hip_train.so, liblsq_hip_linear.so, liblsq_hip_linear_fp.so and
- * liblsq_hip_linear_train.so.
+ * of its own beside liblsq_hip.so, liblsq_hip_train.so, liblsq_hip_linear.so, liblsq_hip_linear_fp.so,
+ * liblsq_hip_linear_train.so and liblsq_hip_linear_wgrad_half.so (lsq_hip_linear_wgrad_half.h: the same kernels, compiled from
+ * the same source, on bf16 / fp16 operands).
  *
  * Conventions are those of lsq_hip.h: device pointers owned by the caller (the library allocates nothing; the workspace
  * is the caller's), `stream` is a hipStream_t passed as void* (NULL = default stream), every function returns 0, a

@@ -8,37 +8,9 @@
 
 #include "lsq_hip_linear_train_half.h"
 #include "../linear_train/lsq_linear_dgrad.h"
+#include "../lsq_ste_one.h"           // ste_one, kMaxK: the straight-through estimator of ../lsq_ste.hip
 
 namespace {
-
-constexpr int kMaxK = LSQ_MAX_PLANES;
-
-// ste_one of ../lsq_ste.hip, restated (this library links none of liblsq_hip.so's objects): the gradient of the quantizer
-// chain's value through the straight-through estimator of every sign and the clamp in front.
-__device__ __forceinline__ float ste_one(float xv, float gv, const float (&v)[kMaxK], int k, float alpha) {
-  const bool inside = alpha < 0.f || (xv >= -alpha && xv <= alpha);        // clamp backward: min <= x <= max
-  const float xc = alpha >= 0.f ? fminf(fmaxf(xv, -alpha), alpha) : xv;
-  float r = 0.f;
-  float d[kMaxK];
-#pragma unroll
-  for (int i = 0; i < kMaxK; ++i) {
-    if (i < k) {
-      d[i] = xc - r;
-      r = r + v[i] * (d[i] >= 0.f ? 1.f : -1.f);       // sign(+-0) = +1
-    }
-  }
-  float G = gv, acc = 0.f;
-#pragma unroll
-  for (int i = kMaxK - 1; i >= 0; --i) {
-    if (i < k) {
-      const float t = (fabsf(d[i]) <= 1.f) ? G * v[i] : 0.f;
-      acc += t;
-      G -= t;
-    }
-  }
-  if (k == 0) acc = gv;
-  return inside ? acc : 0.f;
-}
 
 // The epilogue: x given -> ste_one against the step's input with the sample's scales; then fp32 or one rounding into T.
 template <class T>

@@ -1,356 +1,23 @@
-// lsq_linear_signx_wgrad: fp32 gradient rows (transposed) x the sign planes of the quantized input with the sum over the
-// ROWS, on the bf16 matrix cores of gfx950 (v_mfma_f32_32x32x16_bf16) -- the weight gradient of QuantLinear with binary
-// activations.
-//
-// As a GEMM:  gwq[o][f] = sum_p sum_m (gy[m][o] xs[p][m / T]) b_p[m][f],  D rows = O output features, K = M rows (per
-// plane), D columns = F input features; fragment layout, the hi / lo split and the sign-bit expansion:
-// csrc/linear/lsq_signw_mma.h.
-//   * INPUT: a first kernel (sign_image) walks x row-major and writes X[p][ceil(M / 64)][ceil16(F)]: bit j of word
-//     [p][w][f] = the chain's sign b_p at row 64 w + j, feature f.  A lane owns one feature and ORs the bits of 64 rows into
-//     its kx words -- the layout the GEMM wants is the natural one, no ballot, no LDS.  After it a lane's B fragment is 8
-//     consecutive bits of one word of its column.
-//   * GRADIENT: a = fl32(gy xs[p][m / T]) -- the scale is per (plane, k), so it goes into A and all planes add into ONE
-//     accumulator --, then split.  The A fragment is 8 consecutive m of one o while gy is contiguous in o: the tile goes
-//     through LDS transposed.  Rows past M are staged as 0 (their image bits are 0 and would read as -1).
-//   * Output features past O and columns past F read a valid row / column and are never stored.
-// Three kernels behind the one entry point (selected from O and F, see lsq_linear_signx_wgrad):
-//   sign_image   one wave per 64 rows x 64 features.
-//   wgrad_tiled  O x F tiles of 128 x 128 or 64 x 64, four waves (2 x 2), over ceil(M / 64) * kx stages (word-major, the
-//                planes of a word inside it: the gradient rows of a word are loaded ONCE for all planes); per stage the
-//                workgroup scales and splits its gradient tile into LDS, o-major.  A staging thread holds rows m, m + 1 of
-//                four output features and stores four packed bf16 pairs; the lanes of a half-wave are 2 groups of four
-//                output features x 16 row pairs, which puts the 32 stores of an instruction on 32 different banks.  The
-//                next stage's gradients, scales and image words are loaded into registers while the MFMAs of this one run.
-//   wgrad_split  few tiles (LeNet fc1, the ResNet head): one 32 x 32 tile of gwq per workgroup, the (word, plane, 16-row
-//                step) units split over 8 waves, each reading, scaling, splitting and multiplying its own range straight from
-//                global memory; the partial sums meet in LDS and are added in wave order.
-
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
+// liblsq_hip_linear_wgrad.so: lsq_linear_signx_wgrad, fp32 gradient rows (transposed) x the sign planes of the quantized input
+// with the sum over the ROWS, on the bf16 matrix cores of gfx950 (v_mfma_f32_32x32x16_bf16) -- the weight gradient of
+// QuantLinear with binary activations.
+// The kernels and the host logic live in lsq_linear_wgrad_core.h, shared with liblsq_hip_linear_wgrad_half.so; this library
+// instantiates them on fp32 operands with the plain fp32 store.
 
 #include "lsq_hip_linear_wgrad.h"
-#include "../linear/lsq_signw_mma.h"
-
-namespace {
-
-struct Args {
-  const float* gy;                    // [M][O]
-  const unsigned long long* img;      // sign image [kx][nwm][fpad]
-  const float* xscales;               // [kx][N]
-  float* gwq;                         // [O][F]
-  int M, N, T, F, O, kx, fpad, nwm;   // fpad = ceil16(F); nwm = ceil(M / 64)
-  int ntf;                            // wgrad_split: tiles of 32 columns
-};
-
-// ---------------------------------------------------------------------------------------------------------------------
-// X[p][w][f] bit j = [d_p >= 0] of the quantizer chain at row 64 w + j, feature f (lsq_ste.hip: ste_one): one wave per
-// block of 64 rows x 64 features (grid-stride over the blocks).  Rows >= M and features >= F leave zero bits; the words of
-// columns f < ceil16(F) are written.
-__global__ __launch_bounds__(256) void sign_image(const float* __restrict__ x, const float* __restrict__ xs,
-                                                  unsigned long long* __restrict__ img, int kx, float alpha, int M, int N,
-                                                  int T, int F, int fpad, int nwm, int nwf, long long blocks) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const long long stride = (long long)gridDim.x * 4;
-  for (long long b = (long long)blockIdx.x * 4 + wave; b < blocks; b += stride) {
-    const int fw = (int)(b % nwf);
-    const int w = (int)(b / nwf);
-    const int f = fw * 64 + lane;
-    const bool live = f < F;
-    const float* __restrict__ xcol = x + (live ? f : 0);
-    unsigned long long word[LSQ_MAX_PLANES];
-#pragma unroll
-    for (int i = 0; i < LSQ_MAX_PLANES; ++i) word[i] = 0ull;
-    const int mb = w * 64;
-    int n = T == 1 ? mb : mb / T;
-    int rem = mb - n * T;
-    for (int j0 = 0; j0 < 64 && mb + j0 < M; j0 += 8) {
-      float xv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int m = min(mb + j0 + j, M - 1);
-        xv[j] = xcol[(long long)m * F];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (mb + j0 + j < M) {
-          const float xc = alpha >= 0.f ? fminf(fmaxf(xv[j], -alpha), alpha) : xv[j];
-          float r = 0.f;
-#pragma unroll
-          for (int i = 0; i < LSQ_MAX_PLANES; ++i) {
-            if (i < kx) {
-              const float v = xs[(long long)i * N + n];
-              const float d = xc - r;
-              const bool pos = d >= 0.f;                           // sign(+-0) = +1
-              word[i] |= (unsigned long long)pos << (j0 + j);
-              r = r + v * (pos ? 1.f : -1.f);
-            }
-          }
-          if (++rem == T) { rem = 0; ++n; }
-        }
-      }
-    }
-    if (f < fpad) {
-#pragma unroll
-      for (int i = 0; i < LSQ_MAX_PLANES; ++i)
-        if (i < kx) img[((long long)i * nwm + w) * fpad + f] = live ? word[i] : 0ull;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// (the 4-byte-load variant of the 128 x 128 tile keeps 32 clamped addresses live: one workgroup per CU, no scratch)
-template <int RB, int CB, bool VEC>
-__global__ __launch_bounds__(256, (RB == 2 && !VEC) ? 1 : 2) void wgrad_tiled(Args a) {
-  constexpr int BO = 64 * RB;
-  constexpr int kPass = BO / 32;                      // wave tasks (16 output features x 32 rows) per wave and stage
-  __shared__ __attribute__((aligned(16))) unsigned char s_a[2 * BO * kPitch];    // hi rows [BO], then lo rows [BO]
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int col = lane & 31, hh = lane >> 5;
-  const int wr = wid >> 1, wc = wid & 1;              // the wave's block of rows / columns in the tile
-  const int f0 = blockIdx.x * 64 * CB;
-  const int o0 = blockIdx.y * BO;
-  // staging role: four output features (sq) and one pair of rows (sp) of every task; a half-wave = 2 quads x 16 pairs
-  const int sq = ((lane & 1) + 2 * hh) * 4, sp = (lane >> 1) & 15;
-
-  float gr[kPass][2][4], sc[kPass][2];
-  unsigned long long wn[1][CB], wcur[1][CB];      // [1]: one accumulator set for all planes (mma_stage<NQ = 1>)
-  auto load_g = [&](int w) {
-#pragma unroll
-    for (int i = 0; i < kPass; ++i) {
-      const int t = wid + 4 * i;
-      const int o = o0 + (t >> 1) * 16 + sq;
-      const int m = w * 64 + (t & 1) * 32 + 2 * sp;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const float* p = a.gy + (long long)min(m + e, a.M - 1) * a.O;
-        if constexpr (VEC) {
-          const float4 v = *reinterpret_cast<const float4*>(p + min(o, a.O - 4));
-          gr[i][e][0] = v.x; gr[i][e][1] = v.y; gr[i][e][2] = v.z; gr[i][e][3] = v.w;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) gr[i][e][j] = p[min(o + j, a.O - 1)];
-        }
-      }
-    }
-  };
-  auto load_sw = [&](int w, int p) {
-#pragma unroll
-    for (int i = 0; i < kPass; ++i) {
-      const int t = wid + 4 * i;
-      const int m = w * 64 + (t & 1) * 32 + 2 * sp;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int mm = min(m + e, a.M - 1);
-        sc[i][e] = a.xscales[(long long)p * a.N + (a.T == 1 ? mm : mm / a.T)];
-      }
-    }
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb) {
-      const int f = min(f0 + wc * 32 * CB + cb * 32 + col, a.fpad - 1);
-      wn[0][cb] = a.img[((long long)p * a.nwm + w) * a.fpad + f];
-    }
-  };
-  auto stash = [&](int w) {
-#pragma unroll
-    for (int i = 0; i < kPass; ++i) {
-      const int t = wid + 4 * i;
-      const int ol = (t >> 1) * 16 + sq;
-      const int mp = (t & 1) * 16 + sp;
-      const int m = w * 64 + 2 * mp;
-      unsigned char* d = s_a + ol * kPitch + mp * 4;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float c0 = m < a.M ? __fmul_rn(gr[i][0][j], sc[i][0]) : 0.f;
-        const float c1 = m + 1 < a.M ? __fmul_rn(gr[i][1][j], sc[i][1]) : 0.f;
-        unsigned h, l;
-        split_pair(c0, c1, h, l);
-        *reinterpret_cast<unsigned*>(d + j * kPitch) = h;
-        *reinterpret_cast<unsigned*>(d + j * kPitch + BO * kPitch) = l;
-      }
-    }
-  };
-
-  f32x16 acc[1][RB][CB];
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[0][rb][cb][i] = 0.f;
-
-  load_g(0);
-  load_sw(0, 0);
-  for (int w = 0; w < a.nwm; ++w) {
-    for (int p = 0; p < a.kx; ++p) {
-      __syncthreads();                                // every wave is done reading the previous stage
-      stash(w);
-#pragma unroll
-      for (int cb = 0; cb < CB; ++cb) wcur[0][cb] = wn[0][cb];
-      __syncthreads();
-      if (p + 1 < a.kx) {                             // in flight during the MFMAs below
-        load_sw(w, p + 1);
-      } else if (w + 1 < a.nwm) {
-        load_g(w + 1);
-        load_sw(w + 1, 0);
-      }
-      mma_stage(s_a, BO * kPitch, wr * 32 * RB, col, hh, wcur, acc);
-    }
-  }
-
-#pragma unroll
-  for (int cb = 0; cb < CB; ++cb) {
-    const int f = f0 + wc * 32 * CB + cb * 32 + col;
-    if (f >= a.F) continue;
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int o = d_row(o0 + wr * 32 * RB + rb * 32, i, hh);
-        if (o >= a.O) continue;
-        a.gwq[(long long)o * a.F + f] = acc[0][rb][cb][i];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * kSplitWaves) void wgrad_split(Args a) {
-  __shared__ float s_red[kSplitWaves][1][16][64];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int col = lane & 31, hh = lane >> 5;
-  const int f0 = ((int)blockIdx.x % a.ntf) * 32;
-  const int o0 = ((int)blockIdx.x / a.ntf) * 32;
-  const int units = a.nwm * a.kx * 4;                 // (word, plane, 16-row step), in this order
-  const int per = (units + kSplitWaves - 1) / kSplitWaves;
-  const int u0 = wid * per, u1 = min(units, u0 + per);
-  const float* gcol = a.gy + min(o0 + col, a.O - 1);  // the lane's A row (an output feature)
-  const int fl = min(f0 + col, a.fpad - 1);           // the lane's B column
-  const unsigned char* bytes = reinterpret_cast<const unsigned char*>(a.img);
-
-  f32x16 acc[1];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[0][i] = 0.f;
-
-  float gn[8], sn[8];
-  unsigned bn = 0;
-  int mbn = 0;
-  int w = 0, p = 0, s = 0;                            // the unit `load` reads next
-  if (u0 < u1) {
-    w = u0 / (4 * a.kx);
-    const int rest = u0 - w * 4 * a.kx;
-    p = rest >> 2;
-    s = rest & 3;
-  }
-  auto load = [&]() {
-    const int mb = w * 64 + 16 * s + 8 * hh;
-    const int mc = min(mb, a.M - 1);
-    int n = a.T == 1 ? mc : mc / a.T;
-    int rem = mc - n * a.T;
-    const float* xs = a.xscales + (long long)p * a.N;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      gn[j] = gcol[(long long)min(mb + j, a.M - 1) * a.O];
-      sn[j] = xs[min(n, a.N - 1)];
-      if (++rem == a.T) { rem = 0; ++n; }
-    }
-    bn = bytes[(((long long)p * a.nwm + w) * a.fpad + fl) * 8 + 2 * s + hh];
-    mbn = mb;
-    if (++s == 4) {
-      s = 0;
-      if (++p == a.kx) { p = 0; ++w; }
-    }
-  };
-
-  if (u0 < u1) load();
-  for (int u = u0; u < u1; ++u) {
-    float c[8];
-    const int mb = mbn;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) c[j] = mb + j < a.M ? __fmul_rn(gn[j], sn[j]) : 0.f;
-    const Frag bw = expand8(bn);
-    if (u + 1 < u1) load();                           // in flight during the MFMAs below
-    Frag hi, lo;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) split_pair(c[2 * d], c[2 * d + 1], hi.u[d], lo.u[d]);
-    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(hi.v, bw.v, acc[0], 0, 0, 0);
-    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(lo.v, bw.v, acc[0], 0, 0, 0);
-  }
-
-  split_reduce(s_red, acc, wid, lane);
-
-  // wave g finishes registers 2 g and 2 g + 1 of the tile: the partial sums added in wave order
-  const int f = f0 + col;
-  if (f >= a.F) return;
-#pragma unroll
-  for (int ii = 0; ii < 2; ++ii) {
-    const int i = 2 * wid + ii;
-    const int o = o0 + (i & 3) + 8 * (i >> 2) + 4 * hh;       // d_row of lsq_signw_mma.h, written out (see there)
-    if (o >= a.O) continue;
-    a.gwq[(long long)o * a.F + f] = split_sum(s_red, 0, i, lane);
-  }
-}
-
-int launch(const Args& a, TileRule rule, bool vec, hipStream_t st) {
-  const TileKernels<Args> k = {{wgrad_split, wgrad_split},
-                               {wgrad_tiled<2, 2, false>, wgrad_tiled<2, 2, true>},
-                               {wgrad_tiled<1, 1, false>, wgrad_tiled<1, 1, true>}};
-  auto grid = [&](int t) {                            // split: the tiles in x, columns fastest; tiled: x = columns, y = rows
-    const unsigned rows = (unsigned)((a.O + t - 1) / t), cols = (unsigned)((a.F + t - 1) / t);
-    return t == 32 ? dim3((unsigned)a.ntf * rows) : dim3(cols, rows);
-  };
-  return launch_tiles(k, a, rule, vec, grid, st);
-}
-
-bool in_limits(int kx, int64_t N, int64_t T, int64_t F, int64_t O) {
-  return kx >= 1 && kx <= LSQ_MAX_PLANES && N > 0 && T > 0 && F > 0 && O > 0 && N <= 65535 && T < (1ll << 31) &&
-         N * T < (1ll << 31) && F < (1ll << 22) && O < (1ll << 21);
-}
-
-}  // namespace
+#include "lsq_linear_wgrad_core.h"
 
 extern "C" int lsq_linear_wgrad_abi_version(void) { return LSQ_LINEAR_WGRAD_ABI_VERSION; }
 
 extern "C" size_t lsq_linear_signx_wgrad_workspace_bytes(int kx, int64_t N, int64_t T, int64_t F, int64_t O) {
-  if (!in_limits(kx, N, T, F, O)) return 0;
-  return (size_t)kx * (size_t)((N * T + 63) / 64) * (size_t)((F + 15) / 16 * 16) * sizeof(unsigned long long);
+  return workspace_bytes_of(kx, N, T, F, O);
 }
 
 extern "C" int lsq_linear_signx_wgrad(const float* gy, const float* x, int kx, const float* xscales, float clamp_alpha,
                                       int64_t N, int64_t T, int64_t F, int64_t O, float* gwq, void* workspace,
                                       size_t workspace_bytes, void* stream) {
   if (!gy || !x || !xscales || !gwq) return LSQ_E_NULL;
-  if (N <= 0 || T <= 0 || F <= 0 || O <= 0) return LSQ_E_SHAPE;
-  if (!in_limits(kx, N, T, F, O)) return LSQ_E_UNSUPPORTED;
-  if (!workspace || ((uintptr_t)workspace & 7) ||
-      workspace_bytes < lsq_linear_signx_wgrad_workspace_bytes(kx, N, T, F, O))
-    return LSQ_E_WORKSPACE;
-  Args a = {};
-  a.gy = gy;
-  a.img = (const unsigned long long*)workspace;
-  a.xscales = xscales;
-  a.gwq = gwq;
-  a.M = (int)(N * T);
-  a.N = (int)N;
-  a.T = (int)T;
-  a.F = (int)F;
-  a.O = (int)O;
-  a.kx = kx;
-  a.fpad = (int)((F + 15) / 16 * 16);
-  a.nwm = (a.M + 63) / 64;
-  a.ntf = (a.F + 31) / 32;
-  hipStream_t st = (hipStream_t)stream;
-
-  const int nwf = (a.F + 63) / 64;
-  const long long blocks = (long long)a.nwm * nwf;                // blocks of 64 rows x 64 features, one wave each
-  const long long sgrid = (blocks + 3) / 4;
-  hipLaunchKernelGGL(sign_image, dim3((unsigned)(sgrid < (1ll << 20) ? sgrid : (1ll << 20))), dim3(256), 0, st, x, xscales,
-                     (unsigned long long*)workspace, kx, clamp_alpha, a.M, a.N, a.T, a.F, a.fpad, a.nwm, nwf, blocks);
-  int e = (int)hipGetLastError();
-  if (e) return e;
-
-  // 16-byte gradient loads where every row starts on 16 bytes (same values, same bits as the 4-byte loads)
-  const bool vec = ((uintptr_t)gy & 15) == 0 && O % 4 == 0;
-  return launch(a, tile_rule(O, F), vec, st);
+  if (int e = check_call(kx, N, T, F, O, workspace, workspace_bytes)) return e;
+  const EpiStore epi = {gwq};
+  return launch_wgrad(gy, x, kx, xscales, clamp_alpha, N, T, F, O, epi, workspace, (hipStream_t)stream);
 }

@@ -644,6 +644,7 @@ conv_train_half_lib, conv_train_half_library_path, CONV_TRAIN_HALF_ABI_VERSION =
 conv_proj_lib, conv_proj_library_path, CONV_PROJ_ABI_VERSION = _sublib('conv_proj')
 conv_xnor_half_lib, conv_xnor_half_library_path, CONV_XNOR_HALF_ABI_VERSION = _sublib('conv_xnor_half')
 train_half_lib, train_half_library_path, TRAIN_HALF_ABI_VERSION = _sublib('train_half')
+linear_wgrad_half_lib, linear_wgrad_half_library_path, LINEAR_WGRAD_HALF_ABI_VERSION = _sublib('linear_wgrad_half')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -897,6 +898,56 @@ def linear_signx_wgrad(gy: torch.Tensor, x: torch.Tensor, xscales: torch.Tensor,
         check(wl.lsq_linear_signx_wgrad(gy.data_ptr(), x.data_ptr(), kx, xscales.data_ptr(), float(alpha), N, T, F, O,
                                         gwq.data_ptr(), *_ws_args(ws), stream_ptr(dev)), 'lsq_linear_signx_wgrad')
     return gwq
+
+
+# ---- the linear layer's 16-bit weight-gradient library (include/lsq_hip_linear_wgrad_half.h)
+def linear_signx_wgrad_half(gy: torch.Tensor, x: torch.Tensor, xscales: torch.Tensor, alpha: float, N: int, T: int, F: int,
+                            O: int, weight: Optional[torch.Tensor] = None,
+                            wscales: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[O, F] fp32 in one call (lsq_linear_signx_wgrad_half): gy^T @ x_q for the bf16 / fp16 gradient rows ``gy`` [N * T, O]
+    and the layer's input ``x`` [N * T, F] of the same type before the clamp (any 2-byte-aligned data pointers), with the
+    per-(plane, sample) scales ``xscales`` [kx, N] fp32 and the clamp ``alpha``, the bound ALREADY ROUNDED into the type
+    (negative: none) -- bit for bit ``linear_signx_wgrad(gy.float(), x.float(), ...)``; with ``weight`` [O, F] fp32 and
+    ``wscales`` [kw, O] fp32 the product goes through the straight-through estimator of the weight quantizer in the kernel's
+    epilogue -- bit for bit ``ste_backward(weight, that, wscales, -1.0)``, the step's grad_w.  The sign image lives in the
+    workspace of ``linear_signx_wgrad`` (the same size; cached per (device, stream), rewritten by every call; kernels of one
+    stream run in order)."""
+    what = 'lsq_linear_signx_wgrad_half'
+    N, T, F, O = int(N), int(T), int(F), int(O)
+    M = N * T
+    _check_half(what, 'gy', gy)
+    if x.dtype != gy.dtype:
+        raise TypeError(f'{what}: x must be of gy\'s type {gy.dtype}, got {x.dtype}')
+    if (weight is None) != (wscales is None):
+        raise ValueError(f'{what}: weight and wscales go together')
+    fp32 = {'xscales': xscales} if weight is None else {'xscales': xscales, 'weight': weight, 'wscales': wscales}
+
+    def mismatch():
+        if xscales.dim() != 2 or xscales.shape[1] != N:
+            return 'activation scales and (kx, N)'
+        if weight is not None and (wscales.dim() != 2 or wscales.shape[1] != O or not 1 <= wscales.shape[0] <= MAX_PLANES):
+            return f'weight scales and (1 .. {MAX_PLANES}, O)'
+
+    def problem():
+        if min(N, T, F, O) <= 0 or gy.numel() != M * O or x.numel() != M * F or (weight is not None and weight.numel() != O * F):
+            return (f'bad sizes N={N} T={T} F={F} O={O} for gy of {gy.numel()}, x of {x.numel()}'
+                    + ('' if weight is None else f', weight of {weight.numel()}') + ' elements')
+        subject = mismatch()
+        return None if subject is None else f'{subject} do not match'
+
+    _check_operands(what, fp32, half=(gy, x), problem=problem)
+    kx, dev = xscales.shape[0], gy.device
+    kw = 0 if weight is None else wscales.shape[0]
+    wl = linear_wgrad_half_lib()
+    need = int(wl.lsq_linear_signx_wgrad_half_workspace_bytes(kx, N, T, F, O))
+    ws = _stream_buffer('linear_wgrad', need, dev) if need else None
+    out = torch.empty((O, F), dtype=torch.float32, device=dev)
+    nbytes = 2 * M * O + 2 * M * F + 4 * kx * N + 2 * need + 4 * O * F + (0 if weight is None else 4 * O * F + 4 * kw * O)
+    with _on(out), (_Timed(what, nbytes, 2 * 2 * M * F * O * kx) if _timing is not None else _UNTIMED):     # (hi and lo pass)
+        check(wl.lsq_linear_signx_wgrad_half(gy.data_ptr(), x.data_ptr(), LINEAR_HALF_DTYPES[gy.dtype], kx, xscales.data_ptr(),
+                                             float(alpha), N, T, F, O, ptr(weight), kw, ptr(wscales), out.data_ptr(),
+                                             *_ws_args(ws), stream_ptr(dev)), what)
+    return out
 
 
 # ---- the 16-bit-activation linear-layer library (include/lsq_hip_linear_half.h)

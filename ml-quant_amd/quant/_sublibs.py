@@ -135,6 +135,9 @@ SUBLIBS = (
     _entry('train_half', '|lsq_train_wgrad_half[a-z0-9_]*', {
         'lsq_train_wgrad_half_workspace_bytes': (sz, [gp, i32, i32]),
         'lsq_train_wgrad_half': (i32, [vp, i32, vp, vp, i32, gp, vp, vp, vp, sz, vp])}),
+    _entry('linear_wgrad_half', '|lsq_linear_signx_wgrad_half[a-z0-9_]*', {
+        'lsq_linear_signx_wgrad_half_workspace_bytes': (sz, [i32, i64, i64, i64, i64]),
+        'lsq_linear_signx_wgrad_half': (i32, [vp, vp, i32, i32, vp, f32, i64, i64, i64, i64, vp, i32, vp, vp, vp, sz, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

@@ -35,7 +35,13 @@ forward   ``lsq_act_quant_half`` on (N, T*F, 1, 1) reads the 16-bit samples as t
 backward  grad_x is ONE ``lsq_linear_signw_dgrad_half`` (liblsq_hip_linear_train_half.so): the 16-bit grad_y as it is against
           the forward's own weight planes, the straight-through estimator against the 16-bit x in the kernel's epilogue, a
           16-bit grad_x -- bit for bit ``lsq_ste_backward(x.float(), lsq_linear_signw_dgrad(gy.float())).to(dtype)``; grad_w
-          and grad_b are computed in fp32 from one ``gy.float()`` as in the fp32 step.
+          and grad_b are computed in fp32 from one ``gy.float()`` as in the fp32 step (``x.float()``, then ``torch.mm`` or,
+          with ``WGRAD_KERNEL``, ``lsq_linear_signx_wgrad`` on the two copies, then ``lsq_ste_backward``);
+          with ``WGRAD_HALF_KERNEL`` and binary activations grad_w is ONE ``lsq_linear_signx_wgrad_half``
+          (liblsq_hip_linear_wgrad_half.so) instead: the 16-bit grad_y and x as they are, the sign image of x, the
+          straight-through estimator of the weight quantizer in the GEMM's epilogue -- bit for bit
+          ``lsq_ste_backward(weight, lsq_linear_signx_wgrad(gy.float(), x.float()))`` with no fp32 copy of either operand, no
+          x_q and no fp32 product in memory; grad_b on that route is ``gy.sum(dim=0, dtype=torch.float32)``.
 """
 
 import os
@@ -49,6 +55,13 @@ from quant.binary.hip_train_common import step_act_quant, step_planes, step_weig
 # GEMM on the matrix cores) instead of lsq_quant_values + torch.mm -- the counterpart of hip_train.WGRAD_KERNEL; DESIGN 4.13
 # has the measurements.  fp activations keep torch.mm under either setting.
 WGRAD_KERNEL = False
+
+# True: in the 16-bit step (``hip_train_half``) the weight gradient of a layer with binary activations is one
+# lsq_linear_signx_wgrad_half call on the 16-bit grad_y and x (the weight's straight-through estimator in its epilogue) instead
+# of two fp32 copies + lsq_quant_values + torch.mm (or lsq_linear_signx_wgrad) + lsq_ste_backward -- the counterpart of
+# hip_train.WGRAD_HALF_KERNEL; DESIGN 4.29 has the measurements.  Independent of WGRAD_KERNEL and ahead of it in the 16-bit
+# step; fp activations and a missing library keep the routes above.
+WGRAD_HALF_KERNEL = False
 
 
 def _half_supported(lin, x, _hip) -> bool:
@@ -190,7 +203,13 @@ class _QuantLinearStepHalf(torch.autograd.Function):
         gx = gw = gb = None
         if need_x:
             gx = _hip.linear_signw_dgrad_half(gy2, wbits, wscales, m, f, o, x.view(m, f), xscales, alpha, T=t).view(x.shape)
-        if need_w or need_b:
+        if need_w and WGRAD_HALF_KERNEL and xscales is not None and os.path.exists(_hip.linear_wgrad_half_library_path()):
+            with torch.autocast('cuda', enabled=False):
+                gw = _hip.linear_signx_wgrad_half(gy2, x.view(m, f), xscales, alpha, n, t, f, o, weight.detach().contiguous(),
+                                                  wscales)
+                if need_b:
+                    gb = gy2.sum(dim=0, dtype=torch.float32)
+        elif need_w or need_b:
             with torch.autocast('cuda', enabled=False):
                 gy32 = gy2.float()
                 if need_b:
