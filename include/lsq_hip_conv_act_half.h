@@ -43,8 +43,8 @@ int lsq_conv_act_half_abi_version(void);
  *   scales       out, [k][N] fp32 (LST: row 1 repeats v1)
  *   status       out, [N] int32 or NULL: free-running LS2 / LST: 1 where the row had a candidate (the ternary extra candidate
  *                counts), 0 where it had none or where the whole sub-sample is +-0 (then v1 = 0); every other call writes 1
- * There is no pre_scale / pre_shift: a batch norm on a 16-bit tensor rounds its output into the type, so it cannot be
- * folded into an exact read.
+ * There is no pre_scale / pre_shift here: a batch norm on a 16-bit tensor rounds its output into the type.  The fold that
+ * applies that rounding inside the read is lsq_hip_conv_act_bn_half.h's, a library of its own.
  *
  * Values.  A row is a sample, flattened NCHW, M = C H W elements.  Every element is converted to fp32 exactly (subnormals
  * kept) and clamped to +-a, then runs the chain of lsq_act_quant operation for operation: result_0 = 0, res_0 = c,

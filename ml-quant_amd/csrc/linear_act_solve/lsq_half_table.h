@@ -1,5 +1,6 @@
 // The count-table solve of the 16-bit quantizers: the optimal v1 of quant/binary/optimal.py (ls-2 / ls-T,
-// free-running) of a bf16 / fp16 row.  conv_act_half/lsq_conv_act_half.hip (1024 threads a sample) calls solve_v1;
+// free-running) of a bf16 / fp16 row.  conv_act_half/lsq_conv_act_half_core.h (1024 threads a sample; with the
+// folded batch norm of DESIGN 4.30 as the element transform `xf`) calls solve_v1;
 // lsq_linear_act_solve.hip (512 threads a row) shares the table's constants, phys(), key_value and the host side
 // and keeps pass 1 to the argmin written in line -- the same statements: a change to either goes into both.
 // The table (one count per 15-bit magnitude key, dynamic LDS up to key(alpha), swizzled by phys()) and the steps PASS 1, PLAN
@@ -50,9 +51,19 @@ __device__ __forceinline__ double key_value(unsigned key) { return (double)to_f3
 // value) and int ternary (read from it, not passed as four values: DESIGN 4.25).  hist: (kmax / kSlice + 1) * kSlice counts.
 // VEC16: the row starts on 16 bytes, len % 8 == 0.  Every thread gets the same candidate (order == kNoKey: none, value 0)
 // and the same sum `total` of the sub-sample's magnitudes.
-template <bool F16, bool VEC16, int THREADS, class ARGS>
+// xf: an element transform applied to the 16 bits of every element pass 1 counts (the row is then the transformed row):
+// xf.channel(index) is what the transform needs of the element at `index` of the row, xf(bits, that) the transformed bits.  On
+// the VEC16 path channel() is asked once per group of 8 elements, at the group's first: a transform that depends on the index
+// must be constant over aligned groups of 8.  The default is the identity and compiles to nothing.
+struct Identity {
+  struct Channel {};
+  __device__ __forceinline__ Channel channel(long long) const { return {}; }
+  __device__ __forceinline__ unsigned operator()(unsigned h, const Channel&) const { return h; }
+};
+
+template <bool F16, bool VEC16, int THREADS, class ARGS, class XF = Identity>
 __device__ __forceinline__ Best solve_v1(const ARGS& a, const unsigned short* __restrict__ xrow, long long len, unsigned* hist,
-                                         Shared<THREADS>& sh, double& total) {
+                                         Shared<THREADS>& sh, double& total, const XF& xf = XF()) {
   static_assert(std::is_same_v<decltype(ARGS::skip), int> && std::is_same_v<decltype(ARGS::n), unsigned> &&
                     std::is_same_v<decltype(ARGS::kmax), unsigned> && std::is_same_v<decltype(ARGS::ternary), int>,
                 "ARGS needs: int skip; unsigned n; unsigned kmax; int ternary");
@@ -82,16 +93,20 @@ __device__ __forceinline__ Best solve_v1(const ARGS& a, const unsigned short* __
       const unsigned d[4] = {raw.x, raw.y, raw.z, raw.w};
       const unsigned r = (unsigned)((8ll * g) % skip);
       unsigned pick = r ? (unsigned)skip - r : 0u;    // the group's first sub-sampled element
+      const auto ch = xf.channel(8ll * g);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         if ((unsigned)j == pick) {
-          count((d[j >> 1] >> (16 * (j & 1))) & 0xFFFFu);
+          count(xf((d[j >> 1] >> (16 * (j & 1))) & 0xFFFFu, ch));
           pick += (unsigned)skip;
         }
       }
     }
   } else {
-    for (unsigned s = tid; s < n; s += THREADS) count(xrow[(long long)s * skip]);
+    for (unsigned s = tid; s < n; s += THREADS) {
+      const long long at = (long long)s * skip;
+      count(xf(xrow[at], xf.channel(at)));
+    }
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {

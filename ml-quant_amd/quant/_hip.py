@@ -12,7 +12,7 @@ import functools
 import warnings
 import os
 import threading
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -645,6 +645,7 @@ conv_proj_lib, conv_proj_library_path, CONV_PROJ_ABI_VERSION = _sublib('conv_pro
 conv_xnor_half_lib, conv_xnor_half_library_path, CONV_XNOR_HALF_ABI_VERSION = _sublib('conv_xnor_half')
 train_half_lib, train_half_library_path, TRAIN_HALF_ABI_VERSION = _sublib('train_half')
 linear_wgrad_half_lib, linear_wgrad_half_library_path, LINEAR_WGRAD_HALF_ABI_VERSION = _sublib('linear_wgrad_half')
+conv_act_bn_half_lib, conv_act_bn_half_library_path, CONV_ACT_BN_HALF_ABI_VERSION = _sublib('conv_act_bn_half')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1081,6 +1082,45 @@ def act_quant_half(x: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: i
         check(conv_act_half_lib().lsq_act_quant_half(
             x.data_ptr(), LINEAR_HALF_DTYPES[x.dtype], ctypes.byref(geom), scheme, k, skip, float(alpha), ptr(forced),
             planes.data_ptr(), scales.data_ptr(), ptr(status), stream_ptr(dev)), what)
+
+
+# ---- the same quantizer with the eval batch norm in front of it folded into the read (include/lsq_hip_conv_act_bn_half.h)
+def act_quant_bn_half(x: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: int, alpha: float, planes: torch.Tensor,
+                      scales: torch.Tensor, forced: Optional[torch.Tensor], pre: Tuple[torch.Tensor, torch.Tensor],
+                      status: Optional[torch.Tensor] = None) -> None:
+    """``act_quant_half`` on ``t = (x.float() * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)).to(x.dtype)`` without ``t``
+    in memory (lsq_act_quant_bn_half): ``pre = (scale, shift)``, fp32 contiguous tensors of C elements on x's device, the
+    folded batch norm; every other argument is ``act_quant_half``'s.  Planes, scales and status are bit for bit what
+    ``act_quant_half`` writes for ``t``."""
+    scheme, k, skip = int(scheme), int(k), int(skip)
+    what = 'lsq_act_quant_bn_half'
+    _check_half(what, 'x', x)
+    pre_scale, pre_shift = pre
+    fp32 = {'scales': scales, 'pre_scale': pre_scale, 'pre_shift': pre_shift}
+    if forced is not None:
+        fp32['forced'] = forced
+
+    def problem():
+        if x.dim() != 4 or x.numel() == 0 or k < 1 or skip < 1:
+            return f'bad sizes k={k}, skip={skip} for x of shape {tuple(x.shape)}'
+        N, C, H, W = x.shape
+        if (geom.N, geom.C, geom.H, geom.W) != (N, C, H, W) or geom.groups < 1 or C % geom.groups or min(geom.pad_h, geom.pad_w) < 0:
+            return f'the geometry and x of shape {tuple(x.shape)} do not match'
+        if pre_scale.numel() != C or pre_shift.numel() != C:
+            return f'pre_scale / pre_shift and the {C} channels of x do not match'
+        words = N * geom.groups * ((C // geom.groups + 63) // 64) * (H + 2 * geom.pad_h) * (W + 2 * geom.pad_w)
+        if (planes.numel() < k * words or tuple(scales.shape) != (k, N) or (forced is not None and tuple(forced.shape) != (k, N))
+                or (status is not None and tuple(status.shape) != (N,))):
+            return 'activation planes / scales / status and (k, geometry) do not match'
+
+    _check_operands(what, fp32, {'planes': planes}, {} if status is None else {'status': status}, half=[x], problem=problem)
+    (N, C, H, W), dev = x.shape, x.device
+    m = C * H * W
+    passes = 1 if forced is not None and k <= 2 else (2 if scheme in (SCHEME_LS2, SCHEME_LST) and forced is None else k)
+    with _on(x), (_Timed(what, N * (2 * m * passes + k * m // 8), 0, f'C{C}_H{H}') if _timing is not None else _UNTIMED):
+        check(conv_act_bn_half_lib().lsq_act_quant_bn_half(
+            x.data_ptr(), LINEAR_HALF_DTYPES[x.dtype], ctypes.byref(geom), scheme, k, skip, float(alpha), pre_scale.data_ptr(),
+            pre_shift.data_ptr(), ptr(forced), planes.data_ptr(), scales.data_ptr(), ptr(status), stream_ptr(dev)), what)
 
 
 # ---- the 16-bit-activation x sign-weight convolution (include/lsq_hip_conv_half.h)

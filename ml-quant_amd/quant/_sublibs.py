@@ -138,6 +138,8 @@ SUBLIBS = (
     _entry('linear_wgrad_half', '|lsq_linear_signx_wgrad_half[a-z0-9_]*', {
         'lsq_linear_signx_wgrad_half_workspace_bytes': (sz, [i32, i64, i64, i64, i64]),
         'lsq_linear_signx_wgrad_half': (i32, [vp, vp, i32, i32, vp, f32, i64, i64, i64, i64, vp, i32, vp, vp, vp, sz, vp])}),
+    _entry('conv_act_bn_half', '|lsq_act_quant_bn_half[a-z0-9_]*', {
+        'lsq_act_quant_bn_half': (i32, [vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

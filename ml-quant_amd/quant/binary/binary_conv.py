@@ -33,6 +33,9 @@ Dispatch of ``forward``:
   * with ``xnor_half`` set on top of ``act_half`` / ``hip_train_half`` (class attribute, False by default): the XNOR
     convolution of a 16-bit input is lsq_xnor_conv2d_half (liblsq_hip_conv_xnor_half.so), which writes the input's type itself
     -- the same bits, no fp32 y --, and ``fused_forward`` hands it non-linearity and 16-bit residuals (DESIGN 4.26);
+  * with ``act_half_bn_fold`` set on top of ``act_half`` (class attribute, False by default): ``fused_forward`` folds an
+    eval-mode ``pre_bn`` of a 16-bit input into the quantizer's read, lsq_act_quant_bn_half
+    (liblsq_hip_conv_act_bn_half.so), instead of running it in torch (DESIGN 4.30);
   * anything else (CPU tensors, grouped / dilated training convolutions, 16-bit inputs with binary activations without
     ``act_half`` or with ``fp`` activations without ``fp_half``, 16-bit weights, an autocast of another type) -> the torch
     formulation in ``quant.binary``.
@@ -117,6 +120,14 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: own; False: lsq_xnor_conv2d + ``.to()`` and the composition in torch, the default whatever the measurement says in the
     #: change that adds it
     xnor_half = False
+
+    #: with ``act_half`` and ``act_half_kernel``: ``fused_forward`` on a bf16 / fp16 CUDA input with binary activations does
+    #: not run an eval-mode ``pre_bn`` (running statistics) in torch but hands its folded (scale, shift) to the quantizer's
+    #: read (lsq_act_quant_bn_half): one read and one write of the activation tensor fewer.  The result is bit for bit the
+    #: layer on ``(x.float() * scale + shift).to(x.dtype)``, which is within one rounding of the type of torch's own batch
+    #: norm but not its bits.  A switch of its own; False: torch's batch norm in front of lsq_act_quant_half, the default
+    #: whatever the measurement says in the change that adds it
+    act_half_bn_fold = False
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
@@ -226,17 +237,25 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         shortcut additions into the convolution's epilogue, so none of them is a separate pass over HBM;
         elsewhere it is the plain composition of the modules."""
         xin = None
+        # act_half_bn_fold: the batch norm of a 16-bit input goes into the quantizer's read (lsq_act_quant_bn_half) instead of
+        # a torch pass of its own -- here and in the composition below
+        fold = self.act_half_bn_fold and pre_bn is not None and self._folds_half_bn(x, pre_bn)
         if self.xnor_half and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and self.x_quant != 'fp':
             # a 16-bit input with ``xnor_half``: the batch norm in torch in front of the quantizer (lsq_act_quant_half folds
-            # none), then non-linearity and 16-bit residuals in the epilogue of lsq_xnor_conv2d_half -- one launch, one
-            # rounding.  Residuals of another type or shape take the composition below.
+            # none; with ``act_half_bn_fold`` lsq_act_quant_bn_half reads through it), then non-linearity and 16-bit residuals
+            # in the epilogue of lsq_xnor_conv2d_half -- one launch, one rounding.  Residuals of another type or shape take
+            # the composition below.
             if isinstance(res_pre, ProjectionShortcut):
                 res_pre = res_pre.tensor()
             if isinstance(res_post, ProjectionShortcut):
                 res_post = res_post.tensor()
-            xin = x if pre_bn is None else pre_bn(x)
-            if self._wants_hip(xin) and self._half_epilogue_fits(xin, res_pre, res_post, prelu):
-                return self._forward_hip(xin, None, relu, res_pre, res_post, prelu, None, res_ready)
+            if fold:
+                if self._half_epilogue_fits(x, res_pre, res_post, prelu):
+                    return self._forward_hip(x, pre_bn, relu, res_pre, res_post, prelu, None, res_ready)
+            else:
+                xin = x if pre_bn is None else pre_bn(x)
+                if self._wants_hip(xin) and self._half_epilogue_fits(xin, res_pre, res_post, prelu):
+                    return self._forward_hip(xin, None, relu, res_pre, res_post, prelu, None, res_ready)
         if (x.dtype == torch.float32 and self._wants_hip(x)
                 and (pre_bn is None or (not pre_bn.training and pre_bn.track_running_stats))):
             # next_q = (batch norm or None, QuantConv2d) that will consume the result: with 1-bit activations on both
@@ -250,7 +269,10 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             res_post = res_post.tensor()
         if res_ready is not None:
             torch.cuda.current_stream(x.device).wait_event(res_ready)
-        y = self(xin if xin is not None else (x if pre_bn is None else pre_bn(x)))
+        if fold:                          # the layer alone on the kernels, the batch norm in its quantizer's read
+            y = self._forward_hip(x, pre_bn)
+        else:
+            y = self(xin if xin is not None else (x if pre_bn is None else pre_bn(x)))
         if res_pre is not None:
             y = y + res_pre
         if relu:
@@ -258,6 +280,16 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         if prelu is not None:
             y = F.prelu(y, prelu)
         return y if res_post is None else y + res_post
+
+    def _folds_half_bn(self, x: torch.Tensor, bn: nn.BatchNorm2d) -> bool:
+        """Whether ``fused_forward`` folds ``bn`` into the 16-bit quantizer's read (``act_half_bn_fold``): a bf16 / fp16 CUDA
+        input this layer takes on the kernels (eval mode, ``act_half``: ``_wants_hip`` needs x's type and shape alone, which
+        the batch norm does not change), binary activations, lsq_act_quant_half in use (not the cast comparator), an eval-mode
+        batch norm with running statistics on x's device.  A train-mode layer keeps torch's batch norm: autograd runs
+        through it."""
+        return (self.act_half_bn_fold and self.act_half_kernel and self.x_quant != 'fp' and x.is_cuda
+                and x.dtype in (torch.bfloat16, torch.float16) and not bn.training and bn.track_running_stats
+                and bn.running_mean is not None and bn.running_mean.device == x.device and self._wants_hip(x))
 
     def _half_epilogue_fits(self, x: torch.Tensor, res_pre, res_post, prelu) -> bool:
         """Whether lsq_xnor_conv2d_half's epilogue takes these operands: residuals that are CUDA tensors of the input's type
@@ -367,15 +399,16 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                 torch.cuda.current_stream(x.device).wait_event(res_ready)
         if x.dtype != torch.float32:
             # a 16-bit input (act_half / fp_half): the samples are read as they are (or cast: the comparator), the clamp bound
-            # as Tensor.clamp would round it into their type; the fp32 result is rounded once.  No folded batch norm, no
-            # chaining; a fused epilogue only with xnor_half (elsewhere fused_forward composes it in torch).
+            # as Tensor.clamp would round it into their type; the fp32 result is rounded once.  A folded batch norm only where
+            # fused_forward hands one down (act_half_bn_fold: binary activations on lsq_act_quant_bn_half), no chaining; a
+            # fused epilogue only with xnor_half (elsewhere fused_forward composes it in torch).
             x16 = x.contiguous()
             if self.x_quant == 'fp':          # (fp_half_kernel = False: the cast route, the comparator of DESIGN 4.19)
                 _hip.signw_conv2d(x16.float(), self._alpha_in(x.dtype), wbits, wscales, bias, geom, y, wprep=wprep)
                 return y.to(x.dtype)
             k = self.x_approximate.n_planes
             planes, scales = self._act_planes(x16 if self.act_half_kernel else x16.float(), geom, k, _hip,
-                                              (geom.pad_h, geom.pad_w, self.groups, x.dtype), alpha=self._alpha_in(x.dtype))
+                                              (geom.pad_h, geom.pad_w, self.groups, x.dtype), pre, alpha=self._alpha_in(x.dtype))
             self.last_act_scales = scales
             if half_out:
                 # xnor_half: the 16-bit result straight from the convolution's epilogue, with whatever fused_forward handed

@@ -141,7 +141,7 @@ class HipQuantModule:
 
     def _act_planes(self, x, geom, k, _hip, extra: tuple = (), pre=None, alpha: Optional[float] = None):
         """Quantize ``x`` (the samples of ``geom``) with lsq_act_quant -- a bf16 / fp16 4-D convolution input: with
-        lsq_act_quant_half; bf16 / fp16 rows [N, L] of a geometry (N, L, 1, 1): with lsq_linear_act_quant_half, or
+        lsq_act_quant_half (lsq_act_quant_bn_half where ``pre`` is given); bf16 / fp16 rows [N, L] of a geometry (N, L, 1, 1): with lsq_linear_act_quant_half, or
         lsq_linear_act_quant_solve_half where ls-2 / ls-T have no given scales -- into this module's plane workspace of kind
         ``'act'``; returns (planes, scales).
         ``extra``: what the caller's plane layout depends on beyond ``geom``'s N, C, H, W; ``pre``: a folded batch norm for the
@@ -158,6 +158,8 @@ class HipQuantModule:
         alpha = self._alpha() if alpha is None else alpha
         if x.dtype == torch.float32:
             _hip.act_quant(x, geom, xq.hip_scheme, k, self.act_skip, alpha, planes, scales, forced, pre)
+        elif x.dim() == 4 and pre is not None:  # the same with the eval batch norm in front folded into the read
+            _hip.act_quant_bn_half(x, geom, xq.hip_scheme, k, self.act_skip, alpha, planes, scales, forced, pre)
         elif x.dim() == 4:                      # a convolution's 16-bit NCHW input: the convolution's plane layout
             _hip.act_quant_half(x, geom, xq.hip_scheme, k, self.act_skip, alpha, planes, scales, forced)
         elif forced is None and xq.hip_scheme in (_hip.SCHEME_LS2, _hip.SCHEME_LST):
