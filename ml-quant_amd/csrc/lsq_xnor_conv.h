@@ -45,7 +45,7 @@ struct ConvArgs {
   int tap_xoff[64];                    // (kh*dil_h)*Wp + kw*dil_w per tap
   // ---- projection shortcut computed in the epilogue's residual registers (lsq_xnor_conv2d_proj; the PROJ instantiations of
   // lsq_xnor_mfma.hip only): residual[n, o, ho, wo] = sum_c proj_w[o, c] * proj_x[n, c, ho * s, wo * s] + proj_bias[o]
-  const float* proj_x;                 // [N][proj_c][proj_h][proj_w_in] fp32 or null (no projection)
+  const float* proj_x;                 // [N][proj_c][proj_h][proj_w_in] or null (no projection): fp32, in a 16-bit launch of io_dtype
   const float* proj_w;                 // [O][proj_c]
   const float* proj_bias;              // [O] or null
   int proj_c, proj_h, proj_w_in, proj_stride;
@@ -74,6 +74,13 @@ __device__ __forceinline__ float epi_load_nt(const T* p) {
 template <typename T>
 __device__ __forceinline__ void epi_store(T* p, float v) {
   *p = (T)v;
+}
+// A value that stays in registers as it was loaded (a gather issued ahead of its use) and is widened where it is used: the
+// exact widening of epi_load, the identity for float.
+template <typename T>
+__device__ __forceinline__ float epi_widen(T v) {
+  if constexpr (std::is_same<T, __bf16>::value) return __uint_as_float((unsigned)__builtin_bit_cast(unsigned short, v) << 16);
+  else return (float)v;
 }
 
 // The projection operand of lsq_xnor_conv2d_proj's kernel: channels a multiple of 64 (the k order of lsq_pointwise.hip, in

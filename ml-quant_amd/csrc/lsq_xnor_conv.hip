@@ -21,6 +21,7 @@
 
 #include "lsq_xnor_conv.h"
 #include "lsq_hip_conv_proj.h"
+#include "lsq_hip_conv_proj_half.h"
 
 #include <cstdlib>
 
@@ -362,7 +363,7 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
     // 16-bit y and residuals: only the LAST launch reads and writes them; the launches before it are the fp32 kernels on an
     // fp32 workspace that the last one reads as its running sum.  Refusals here, before any launch.
     if (io_dtype != LSQ_DTYPE_BF16 && io_dtype != LSQ_DTYPE_F16) return LSQ_E_UNSUPPORTED;
-    if (chained || with_proj) return LSQ_E_UNSUPPORTED;
+    if (chained) return LSQ_E_UNSUPPORTED;      // (with_proj: lsq_xnor_conv2d_proj_half, one launch, proj->x of io_dtype too)
     if (kw_planes * ((kx + 1) / 2) > 1) {
       const size_t need = sizeof(float) * (size_t)g->N * (size_t)g->O * (size_t)Ho * (size_t)Wo;
       if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3) || workspace_bytes < need) return LSQ_E_WORKSPACE;
@@ -432,6 +433,23 @@ int xnor_conv2d_half(const uint64_t* xplanes, int kx, const float* xscales, cons
   return xnor_conv2d_impl(xplanes, kx, xscales, wbits, wsum, kw_planes, wscales, bias, g, act, act_slope,
                           static_cast<const float*>(res_pre), static_cast<const float*>(res_post), static_cast<float*>(y), stream,
                           nullptr, -1.f, nullptr, nullptr, false, dtype == LSQ_DTYPE_F32 ? -1 : dtype, workspace, workspace_bytes);
+}
+
+// lsq_xnor_conv2d_proj_half of liblsq_hip_conv_proj_half.so (include/lsq_hip_conv_proj_half.h), which links this library for
+// it: y, res_pre, res_post and proj->x are 16-bit tensors of `dtype`.  Every refusal of xnor_conv2d_proj comes first, with its
+// code (among them anything but kx = 2 against one weight plane: the call is one launch and has no workspace).
+int xnor_conv2d_proj_half(const uint64_t* xplanes, int kx, const float* xscales, const uint64_t* wbits, const int32_t* wsum,
+                          int kw_planes, const float* wscales, const float* bias, const lsq_conv_geom* g, int act,
+                          const float* act_slope, const void* res_pre, const void* res_post, const lsq_proj_half* proj, int dtype,
+                          void* y, void* stream) {
+  lsq_proj p = {};
+  if (proj) {
+    p.x = static_cast<const float*>(proj->x); p.w = proj->w; p.bias = proj->bias;
+    p.C = proj->C; p.H = proj->H; p.W = proj->W; p.stride = proj->stride; p.post = proj->post;
+  }
+  return xnor_conv2d_impl(xplanes, kx, xscales, wbits, wsum, kw_planes, wscales, bias, g, act, act_slope,
+                          static_cast<const float*>(res_pre), static_cast<const float*>(res_post), static_cast<float*>(y), stream,
+                          nullptr, -1.f, nullptr, proj ? &p : nullptr, true, dtype == LSQ_DTYPE_F32 ? -1 : dtype);
 }
 
 // 0 for a call of one launch (or a geometry the call refuses), else the fp32 running sum: 4 N O Ho Wo

@@ -63,18 +63,20 @@ constexpr unsigned kM0 = 0x01010101u;
 // B = x -- that instruction's D[o][pixel] is this kernel's accumulator layout, so its sixteen values per lane land in rv[16].
 // Same k order as pointwise_all_kernel (chunks of 64 channels, lane half g supplies channel 64 cc + 32 g + 16 h + 4 q + e):
 // the same fmaf chain, the same bits.  The workgroup's 32 x Cp weights sit in (dynamic) LDS at a pitch of Cp + 4 floats; a
-// lane gathers its pixel's x with 4-byte loads, chunk c + 1 in flight during the MFMAs of chunk c.
+// lane gathers its pixel's x with 4-byte loads (2-byte loads of a 16-bit T, below), chunk c + 1 in flight during the MFMAs of chunk c.
 extern __shared__ __attribute__((aligned(16))) float s_pw[];         // PROJ: [32 out-channels][Cp + 4]
 
 // T (lsq_xnor_conv2d_half): the type of the residuals read and of the y written, float, __bf16 or _Float16.  Nothing but the
 // epilogue's loads and stores knows it (epi_load / epi_store of lsq_xnor_conv.h): the arithmetic is the fp32 one, rounded once
 // at the store.  A 16-bit instantiation is the LAST launch of its call; the fp32 sum of the launches before it is read from
-// a.sum, not from y.
+// a.sum, not from y.  PROJ with a 16-bit T (lsq_xnor_conv2d_proj_half): the projection's x is of type T too -- gathered with
+// 2-byte loads, kept as loaded and widened (exact) in front of the MFMA that multiplies it; proj_w and proj_bias stay fp32 and
+// the projection tile stays in the sixteen fp32 registers rv[], never rounded: y is rounded once, at the store.
 template <int KX, int GG, int TAPS, int NWAVES, int WPC, bool CHAIN, bool FP4, bool PROJ = false, typename T = float>
 __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a) {
   static_assert(!PROJ || (FP4 && !CHAIN), "the projection runs in the unchained fp4 kernel only");
   constexpr bool kF32 = std::is_same<T, float>::value;
-  static_assert(kF32 || (FP4 && !CHAIN && !PROJ), "16-bit epilogue I/O: the unchained fp4 kernel without projection only");
+  static_assert(kF32 || (FP4 && !CHAIN), "16-bit epilogue I/O: the unchained fp4 kernel only");
   constexpr int NT = 64 * NWAVES;
   constexpr int FPS = FP4 ? 1 : 2;               // 16-byte weight fragments per (word, tap) step: int8 K = 32 twice, fp4 K = 64 once
   constexpr int NF = TAPS * GG * FPS;            // 16-byte operand fragments per lane
@@ -341,14 +343,14 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
       // requested before the MFMAs of step s (two register sets of SZ).  MFMA m of the k loop multiplies channel
       // 64 (m >> 5) + 32 hh + (m & 31).  Lanes past the last pixel gather image 0 and store nothing.
       constexpr int SZ = WPC >= 3 ? 16 : 32;     // a whole chunk per set where the registers of two waves per SIMD allow it
-      const float* __restrict__ px = a.proj_x;
+      const T* __restrict__ px = reinterpret_cast<const T*>(a.proj_x);
       const int phw = a.proj_h * a.proj_w_in;
       // 32-bit element offset from uniform bases (the entry point admits proj_x below 2^30 elements)
       const unsigned xo = (unsigned)((ln * a.proj_c + 32 * hh) * phw + cur.ho * a.proj_stride * a.proj_w_in + cur.wo * a.proj_stride);
       const int nsteps = a.proj_c / (2 * SZ);
       auto first_channel = [&](int s) { return 64 * ((s * SZ) >> 5) + ((s * SZ) & 31); };      // (of lane half 0)
-      auto gather = [&](int s, float (&v)[SZ]) {
-        const float* __restrict__ src = px + (long long)first_channel(s) * phw;
+      auto gather = [&](int s, T (&v)[SZ]) {
+        const T* __restrict__ src = px + (long long)first_channel(s) * phw;
 #pragma unroll
         for (int m = 0; m < SZ; ++m) v[m] = (src + (long long)m * phw)[xo];
       };
@@ -356,7 +358,7 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
 #pragma unroll
       for (int i = 0; i < 16; ++i) pacc[i] = 0.f;
       const float* __restrict__ wrow = &s_pw[col * pitch + 32 * hh];
-      auto mfmas = [&](int s, const float (&v)[SZ]) {
+      auto mfmas = [&](int s, const T (&v)[SZ]) {
         const float* __restrict__ wsrc = wrow + first_channel(s);
 #pragma unroll
         for (int h = 0; h < SZ / 16; ++h) {
@@ -365,15 +367,15 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
           for (int q = 0; q < 4; ++q) wf[q] = *reinterpret_cast<const float4*>(wsrc + 16 * h + 4 * q);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].x, v[16 * h + 4 * q + 0], pacc, 0, 0, 0);
-            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].y, v[16 * h + 4 * q + 1], pacc, 0, 0, 0);
-            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].z, v[16 * h + 4 * q + 2], pacc, 0, 0, 0);
-            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].w, v[16 * h + 4 * q + 3], pacc, 0, 0, 0);
+            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].x, epi_widen(v[16 * h + 4 * q + 0]), pacc, 0, 0, 0);
+            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].y, epi_widen(v[16 * h + 4 * q + 1]), pacc, 0, 0, 0);
+            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].z, epi_widen(v[16 * h + 4 * q + 2]), pacc, 0, 0, 0);
+            pacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[q].w, epi_widen(v[16 * h + 4 * q + 3]), pacc, 0, 0, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
       };
-      float xa[SZ], xb[SZ];
+      T xa[SZ], xb[SZ];
       gather(0, xa);
       for (int s = 0; s < nsteps; s += 2) {
         if (s + 1 < nsteps) gather(s + 1, xb);
@@ -693,7 +695,8 @@ int launch(const ConvArgs& a, hipStream_t st) {
 #ifndef LSQ_PROJ_SHAPE
 #define LSQ_PROJ_SHAPE 8, 2
 #endif
-template <int GG>
+// T = __bf16 / _Float16 (lsq_xnor_conv2d_proj_half): the same shape; registers per channel count in DESIGN 4.31.
+template <int GG, typename T = float>
 int launch_proj(const ConvArgs& a, hipStream_t st) {
   constexpr int kShape[2] = {LSQ_PROJ_SHAPE};
   constexpr int NWAVES = kShape[0], WPC = kShape[1];
@@ -701,7 +704,7 @@ int launch_proj(const ConvArgs& a, hipStream_t st) {
   const int n_ot = a.O / 32;
   long long gx = (256 + n_ot - 1) / n_ot;
   if (gx * NWAVES > ntiles) gx = (ntiles + NWAVES - 1) / NWAVES;
-  auto kern = xnor_mfma_kernel<2, GG, 9, NWAVES, WPC, false, true, true>;
+  auto kern = xnor_mfma_kernel<2, GG, 9, NWAVES, WPC, false, true, true, T>;
   static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                        32 * (kProjMaxChannels + 4) * (int)sizeof(float));
   if (raised != hipSuccess) return (int)raised;
@@ -721,21 +724,29 @@ int launch_gg_half(const ConvArgs& a, hipStream_t st) {
   return kXnorMfmaNotEligible;
 }
 
+// lsq_xnor_conv2d_proj (T = float) and lsq_xnor_conv2d_proj_half
+template <typename T>
+int launch_proj_gg(const ConvArgs& a, hipStream_t st) {
+  switch (a.cg) {
+    case 64: return launch_proj<1, T>(a, st);
+    case 128: return launch_proj<2, T>(a, st);
+    case 256: return launch_proj<4, T>(a, st);
+    case 512: return launch_proj<8, T>(a, st);
+  }
+  return kXnorMfmaNotEligible;
+}
+
 template <int KX>
 int launch_gg(const ConvArgs& a, hipStream_t st) {
-  if (a.io_dtype == LSQ_DTYPE_BF16) return launch_gg_half<KX, __bf16>(a, st);
-  if (a.io_dtype == LSQ_DTYPE_F16) return launch_gg_half<KX, _Float16>(a, st);
   if constexpr (KX == 2) {
     if (a.proj_x) {
-      switch (a.cg) {
-        case 64: return launch_proj<1>(a, st);
-        case 128: return launch_proj<2>(a, st);
-        case 256: return launch_proj<4>(a, st);
-        case 512: return launch_proj<8>(a, st);
-      }
-      return kXnorMfmaNotEligible;
+      if (a.io_dtype == LSQ_DTYPE_BF16) return launch_proj_gg<__bf16>(a, st);
+      if (a.io_dtype == LSQ_DTYPE_F16) return launch_proj_gg<_Float16>(a, st);
+      return launch_proj_gg<float>(a, st);
     }
   }
+  if (a.io_dtype == LSQ_DTYPE_BF16) return launch_gg_half<KX, __bf16>(a, st);
+  if (a.io_dtype == LSQ_DTYPE_F16) return launch_gg_half<KX, _Float16>(a, st);
   // (test hook lsq_debug_xnor_impl(2): rounds 2-5's int8 kernel, the fp4 kernel's comparator -- same bits; plain calls only)
   if (a.int8_mfma && !a.xunits && !a.nq_planes32) {
     switch (a.cg) {

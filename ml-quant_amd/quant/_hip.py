@@ -646,6 +646,7 @@ conv_xnor_half_lib, conv_xnor_half_library_path, CONV_XNOR_HALF_ABI_VERSION = _s
 train_half_lib, train_half_library_path, TRAIN_HALF_ABI_VERSION = _sublib('train_half')
 linear_wgrad_half_lib, linear_wgrad_half_library_path, LINEAR_WGRAD_HALF_ABI_VERSION = _sublib('linear_wgrad_half')
 conv_act_bn_half_lib, conv_act_bn_half_library_path, CONV_ACT_BN_HALF_ABI_VERSION = _sublib('conv_act_bn_half')
+conv_proj_half_lib, conv_proj_half_library_path, CONV_PROJ_HALF_ABI_VERSION = _sublib('conv_proj_half')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1238,6 +1239,104 @@ def xnor_conv2d_half(planes: torch.Tensor, k: int, xscales: torch.Tensor, wbits:
                                       ptr(res_post), LINEAR_HALF_DTYPES[dtype], y.data_ptr(), *_ws_args(ws), stream_ptr(dev)),
               what)
     return y
+
+
+# ---- the projection shortcut on 16-bit tensors (include/lsq_hip_conv_proj_half.h)
+def pointwise_conv_half(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int) -> torch.Tensor:
+    """``pointwise_conv`` on a bf16 / fp16 ``x`` [N, C, H, W] (lsq_pointwise_conv_half): fp32 ``w`` [O, C] and ``bias``, fp32
+    arithmetic, the result rounded once into ``x``'s type -- bit for bit ``pointwise_conv(x.float(), ...).to(x.dtype)``.  ``x``
+    may be a contiguous view that starts anywhere in its storage (2-byte alignment)."""
+    what = 'lsq_pointwise_conv_half'
+    _check_half(what, 'x', x)
+    fp32 = {'w': w} if bias is None else {'w': w, 'bias': bias}
+    stride = int(stride)
+
+    def problem():
+        if x.dim() != 4 or w.dim() != 2 or min(*x.shape, *w.shape, stride) < 1:
+            return f'bad sizes: x of shape {tuple(x.shape)}, w of shape {tuple(w.shape)}, stride {stride}'
+        if w.shape[1] != x.shape[1] or (bias is not None and tuple(bias.shape) != (w.shape[0],)):
+            return 'w [O, C] / bias [O] and x [N, C, H, W] do not match'
+
+    _check_operands(what, fp32, half=[x], problem=problem)
+    n, c, h, wd = x.shape
+    o = w.shape[0]
+    y = torch.empty((n, o, (h - 1) // stride + 1, (wd - 1) // stride + 1), dtype=x.dtype, device=x.device)
+    hl = conv_proj_half_lib()
+    lib()                                           # (liblsq_hip_conv_proj_half.so links liblsq_hip.so: the same loaded object)
+    with _on(x), (_Timed(what, 2 * (y.numel() // o) * c + 2 * y.numel(), 2 * y.numel() * c) if _timing is not None else _UNTIMED):
+        check(hl.lsq_pointwise_conv_half(x.data_ptr(), LINEAR_HALF_DTYPES[x.dtype], n, c, h, wd, w.data_ptr(), ptr(bias), o,
+                                         stride, y.data_ptr(), stream_ptr(x.device)), what)
+    return y
+
+
+def xnor_conv2d_proj_half(planes: torch.Tensor, k: int, xscales: torch.Tensor, wbits: torch.Tensor, wsum: torch.Tensor,
+                          wscales: torch.Tensor, bias: Optional[torch.Tensor], geom: ConvGeom, proj: tuple, dtype: torch.dtype,
+                          relu: bool = False, res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
+                          prelu: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None):
+    """``xnor_conv2d_half`` with the projection shortcut ``proj = (x of dtype, w [O, Cp] fp32, bias fp32 or None, stride, post)``
+    computed in the epilogue's residual registers (lsq_xnor_conv2d_proj_half): ``post`` False = it plays ``res_pre``, True =
+    ``res_post``; the other slot may hold a tensor of ``dtype``.  Returns ``(True, y)``, y [N, O, Ho, Wo] of ``dtype`` -- bit for
+    bit ``xnor_conv2d_proj`` on the widened operands followed by ``.to(dtype)``, one rounding --, or ``(False, None)`` --
+    nothing launched -- where the library refuses the call as unsupported.  The caller then runs ``pointwise_conv_half`` +
+    ``xnor_conv2d_half``, which round the shortcut to ``dtype`` first: not the same bits (include/lsq_hip_conv_proj_half.h).
+    ``y``: a contiguous tensor of ``dtype`` and the output's shape to write instead of a new one (2-byte alignment)."""
+    what = 'lsq_xnor_conv2d_proj_half'
+    k = int(k)
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f'{what}: dtype must be torch.bfloat16 or torch.float16, got {dtype}')
+    px, pw, pb, stride, post = proj
+    half = {name: t for name, t in (('proj x', px), ('res_pre', res_pre), ('res_post', res_post), ('y', y)) if t is not None}
+    wrong = [name for name, t in half.items() if not isinstance(t, torch.Tensor) or t.dtype != dtype]
+    if wrong:
+        raise TypeError(f'{what}: {", ".join(wrong)} must be {dtype} tensors')
+    fp32 = {'xscales': xscales, 'wscales': wscales, 'proj w': pw}
+    for name, t in (('bias', bias), ('prelu', prelu), ('proj bias', pb)):
+        if t is not None:
+            fp32[name] = t
+    ho, wo = out_hw(geom)
+    shape = (geom.N, geom.O, ho, wo)
+
+    def problem():
+        if k < 1 or wscales.dim() != 2 or wscales.shape[0] < 1 or min(shape) < 1 or px.dim() != 4 or pw.dim() != 2:
+            return f'bad sizes: k={k}, wscales of shape {tuple(wscales.shape)}, output {shape}, proj x of shape {tuple(px.shape)}'
+        if tuple(xscales.shape) != (k, geom.N) or planes.numel() < k * geom.N * geom.groups * (
+                (geom.C // max(geom.groups, 1) + 63) // 64) * (geom.H + 2 * geom.pad_h) * (geom.W + 2 * geom.pad_w):
+            return 'activation planes / scales and (k, geometry) do not match'
+        if wscales.shape[1] != geom.O or wbits.numel() < wscales.shape[0] * _signw_plane_words(geom) \
+                or tuple(wsum.shape) != (wscales.shape[0], geom.O, geom.KH * geom.KW) \
+                or (bias is not None and tuple(bias.shape) != (geom.O,)):
+            return 'weight planes / sums / scales / bias and (kw, geometry) do not match'
+        if px.shape[0] != geom.N or tuple(pw.shape) != (geom.O, px.shape[1]) or (pb is not None and tuple(pb.shape) != (geom.O,)):
+            return 'proj x [N, Cp, H, W], w [O, Cp] and bias [O] do not match the geometry'
+        if prelu is not None and (relu or prelu.numel() not in (1, geom.O)):
+            return f'prelu of {prelu.numel()} slopes on {geom.O} channels' + (' together with relu' if relu else '')
+        for name, t in half.items():
+            if name != 'proj x' and tuple(t.shape) != shape:
+                return f'{name} of shape {tuple(t.shape)} must have the shape of y, {shape}'
+
+    _check_operands(what, fp32, {'planes': planes, 'wbits': wbits}, {'wsum': wsum}, half=list(half.values()), problem=problem)
+    act, slope = _act(relu, None if prelu is None else prelu.detach(), geom.O)
+    dev, kw, cp = planes.device, wscales.shape[0], px.shape[1]
+    pd = _sublibs.ProjHalf(px.data_ptr(), pw.data_ptr(), ptr(pb), cp, px.shape[2], px.shape[3], int(stride), int(bool(post)))
+    hl = conv_proj_half_lib()
+    lib()                                           # (liblsq_hip_conv_proj_half.so links liblsq_hip.so: the same loaded object)
+    if y is None:
+        y = torch.empty(shape, dtype=dtype, device=dev)
+    m = geom.C * geom.H * geom.W
+    nres = (res_pre is not None) + (res_post is not None)
+    macs = y.numel() * (geom.C // geom.groups) * geom.KH * geom.KW * k * kw
+    # algorithmic bytes: planes read + 16-bit output written + every 16-bit residual tensor read + the projection's gathered
+    # input (one 2-byte value per output pixel and input channel)
+    nbytes = geom.N * k * m // 8 + 2 * y.numel() * (1 + nres) + 2 * (y.numel() // geom.O) * cp
+    with _on(y), (_Timed(what, nbytes, macs, f'C{geom.C}_H{geom.H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
+        code = hl.lsq_xnor_conv2d_proj_half(planes.data_ptr(), k, xscales.data_ptr(), wbits.data_ptr(), wsum.data_ptr(), kw,
+                                            wscales.data_ptr(), ptr(bias), ctypes.byref(geom), act, ptr(slope), ptr(res_pre),
+                                            ptr(res_post), ctypes.byref(pd), LINEAR_HALF_DTYPES[dtype], y.data_ptr(),
+                                            stream_ptr(dev))
+    if code == E_UNSUPPORTED:
+        return False, None
+    check(code, what)
+    return True, y
 
 
 # ---- the convolution layer's training library (include/lsq_hip_conv_train.h)

@@ -44,6 +44,12 @@ class Proj(ctypes.Structure):
                 ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('stride', ctypes.c_int32), ('post', ctypes.c_int32)]
 
 
+class ProjHalf(ctypes.Structure):
+    """Mirror of ``lsq_proj_half``: ``lsq_proj`` with ``x`` of the call's 16-bit type (lsq_xnor_conv2d_proj_half)."""
+
+    _fields_ = Proj._fields_
+
+
 gp = ctypes.POINTER(ConvGeom)
 
 # ---- liblsq_hip.so: {header: prototypes}; quant._hip.lib() applies both (ABI_VERSION and the LSQ_HIP_LIB override live there)
@@ -140,6 +146,10 @@ SUBLIBS = (
         'lsq_linear_signx_wgrad_half': (i32, [vp, vp, i32, i32, vp, f32, i64, i64, i64, i64, vp, i32, vp, vp, vp, sz, vp])}),
     _entry('conv_act_bn_half', '|lsq_act_quant_bn_half[a-z0-9_]*', {
         'lsq_act_quant_bn_half': (i32, [vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp])}),
+    _entry('conv_proj_half', '|lsq_pointwise_conv_half|lsq_xnor_conv2d_proj_half', {
+        'lsq_pointwise_conv_half': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
+        'lsq_xnor_conv2d_proj_half': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, ctypes.POINTER(ProjHalf),
+                                            i32, vp, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

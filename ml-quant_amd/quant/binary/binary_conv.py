@@ -32,7 +32,9 @@ Dispatch of ``forward``:
     lsq_act_quant_half / lsq_signw_conv2d_half forward, one lsq_signw_conv2d_dgrad_half for the input gradient;
   * with ``xnor_half`` set on top of ``act_half`` / ``hip_train_half`` (class attribute, False by default): the XNOR
     convolution of a 16-bit input is lsq_xnor_conv2d_half (liblsq_hip_conv_xnor_half.so), which writes the input's type itself
-    -- the same bits, no fp32 y --, and ``fused_forward`` hands it non-linearity and 16-bit residuals (DESIGN 4.26);
+    -- the same bits, no fp32 y --, and ``fused_forward`` hands it non-linearity and 16-bit residuals; a
+    residual given as a ``ProjectionShortcut`` of a 16-bit input (``quant.models.resnet.PROJ_HALF``) is computed inside that
+    launch, lsq_xnor_conv2d_proj_half (liblsq_hip_conv_proj_half.so, DESIGN 4.31);
   * with ``act_half_bn_fold`` set on top of ``act_half`` (class attribute, False by default): ``fused_forward`` folds an
     eval-mode ``pre_bn`` of a 16-bit input into the quantizer's read, lsq_act_quant_bn_half
     (liblsq_hip_conv_act_bn_half.so), instead of running it in torch (DESIGN 4.30);
@@ -60,14 +62,26 @@ class ProjectionShortcut:
     channels multiples of 64).  Passed as ``res_pre`` or ``res_post``, it is computed inside the XNOR convolution where
     lsq_xnor_conv2d_proj takes the call and by lsq_pointwise_conv in front of it elsewhere -- the same bits either way.
     ``tensor()`` is that separate launch; ``self[rows]`` the shortcut of the samples ``rows`` alone (what a reader of the
-    residual of a few samples needs, e.g. a layer-by-layer check)."""
+    residual of a few samples needs, e.g. a layer-by-layer check).
+
+    ``x`` may be bf16 / fp16 (``quant.models.resnet.PROJ_HALF``; ``w`` and ``b`` stay fp32): the consumer is then
+    lsq_xnor_conv2d_proj_half, which keeps the shortcut in fp32 registers and rounds the block's output once, and ``tensor()``
+    is lsq_pointwise_conv_half, a tensor of ``x``'s type -- the shortcut rounded on its own, so in 16 bits the two are NOT the
+    same bits (include/lsq_hip_conv_proj_half.h)."""
 
     def __init__(self, x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], stride: int) -> None:
         self.x, self.w, self.b, self.stride = x.detach(), w, b, int(stride)
 
     def tensor(self, rows=None) -> torch.Tensor:
         from quant import _hip
-        return _hip.pointwise_conv(self.x if rows is None else self.x[rows], self.w, self.b, self.stride)
+        x = self.x if rows is None else self.x[rows]
+        if x.dtype in (torch.bfloat16, torch.float16):
+            return _hip.pointwise_conv_half(x.contiguous(), self.w, self.b, self.stride)
+        return _hip.pointwise_conv(x, self.w, self.b, self.stride)
+
+    def out_shape(self) -> tuple:
+        n, _, h, w = self.x.shape
+        return (n, self.w.shape[0], (h - 1) // self.stride + 1, (w - 1) // self.stride + 1)
 
     def __getitem__(self, rows) -> torch.Tensor:
         return self.tensor(rows)
@@ -244,10 +258,11 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             # a 16-bit input with ``xnor_half``: the batch norm in torch in front of the quantizer (lsq_act_quant_half folds
             # none; with ``act_half_bn_fold`` lsq_act_quant_bn_half reads through it), then non-linearity and 16-bit residuals
             # in the epilogue of lsq_xnor_conv2d_half -- one launch, one rounding.  Residuals of another type or shape take
-            # the composition below.
-            if isinstance(res_pre, ProjectionShortcut):
+            # the composition below.  A ProjectionShortcut of x's own type (resnet.PROJ_HALF) goes down as it is: the launch
+            # is then lsq_xnor_conv2d_proj_half; one of an fp32 x becomes its fp32 tensor here, as before.
+            if isinstance(res_pre, ProjectionShortcut) and res_pre.x.dtype != x.dtype:
                 res_pre = res_pre.tensor()
-            if isinstance(res_post, ProjectionShortcut):
+            if isinstance(res_post, ProjectionShortcut) and res_post.x.dtype != x.dtype:
                 res_post = res_post.tensor()
             if fold:
                 if self._half_epilogue_fits(x, res_pre, res_post, prelu):
@@ -293,14 +308,22 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
 
     def _half_epilogue_fits(self, x: torch.Tensor, res_pre, res_post, prelu) -> bool:
         """Whether lsq_xnor_conv2d_half's epilogue takes these operands: residuals that are CUDA tensors of the input's type
-        and the output's shape, PReLU slopes in fp32 (1 or one per out-channel)."""
+        and the output's shape, PReLU slopes in fp32 (1 or one per out-channel).  At most one of the residuals may be a
+        ``ProjectionShortcut`` whose ``x`` is such a tensor and whose result has the output's shape (lsq_xnor_conv2d_proj_half,
+        or lsq_pointwise_conv_half in front where that call is refused)."""
         from quant import _hip
         if x.dtype not in (torch.bfloat16, torch.float16) or x.dim() != 4:
             return False
         shape = (x.shape[0], self.out_channels) + tuple(_hip.out_hw(self._geom_of(x, _hip)))
+        if isinstance(res_pre, ProjectionShortcut) and isinstance(res_post, ProjectionShortcut):
+            return False
         for r in (res_pre, res_post):
-            if r is not None and not (isinstance(r, torch.Tensor) and r.is_cuda and r.device == x.device and r.dtype == x.dtype
-                                      and tuple(r.shape) == shape):
+            if isinstance(r, ProjectionShortcut):
+                if not (r.x.is_cuda and r.x.device == x.device and r.x.dtype == x.dtype and r.x.dim() == 4
+                        and r.out_shape() == shape):
+                    return False
+            elif r is not None and not (isinstance(r, torch.Tensor) and r.is_cuda and r.device == x.device and r.dtype == x.dtype
+                                        and tuple(r.shape) == shape):
                 return False
         return prelu is None or (prelu.is_cuda and prelu.dtype == torch.float32 and prelu.numel() in (1, self.out_channels))
 
@@ -355,10 +378,15 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         keep = (planes, units, pre)
         return nxt, chain.PreQuant(conv, bn, planes, units, (n, self.out_channels, ho, wo), _hip.stream_ptr(device)), keep
 
-    def _proj_in_kernel(self, x: torch.Tensor, chain) -> bool:
-        """Whether this call ends in the plain XNOR launch that can compute a projection shortcut itself: fp32 input, binary
-        activations, not a chained 1-bit layer."""
-        return x.dtype == torch.float32 and self.x_quant != 'fp' and not (self.x_quant == 'ls-1' and chain.ENABLED)
+    def _proj_in_kernel(self, x: torch.Tensor, chain, sc: ProjectionShortcut) -> bool:
+        """Whether this call ends in the plain XNOR launch that can compute the projection shortcut ``sc`` itself: binary
+        activations, not a chained 1-bit layer, and an fp32 input with an fp32 ``sc.x`` (lsq_xnor_conv2d_proj) or, with
+        ``xnor_half``, a 16-bit input with an ``sc.x`` of its type (lsq_xnor_conv2d_proj_half)."""
+        if self.x_quant == 'fp' or (self.x_quant == 'ls-1' and chain.ENABLED):
+            return False
+        if x.dtype == torch.float32:
+            return sc.x.dtype == torch.float32
+        return self.xnor_half and sc.x.dtype == x.dtype
 
     def _forward_hip(self, x: torch.Tensor, pre_bn: Optional[nn.BatchNorm2d] = None, relu: bool = False,
                      res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
@@ -369,9 +397,9 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         # a ProjectionShortcut in a residual slot: only the plain two-plane XNOR call at the end computes it itself (at most
         # one: the kernel has one residual array in registers); everywhere else it is a launch of its own, here
         proj = None
-        if isinstance(res_post, ProjectionShortcut) and res_pre is None and self._proj_in_kernel(x, chain):
+        if isinstance(res_post, ProjectionShortcut) and res_pre is None and self._proj_in_kernel(x, chain, res_post):
             proj, res_post = (res_post, True), None
-        elif isinstance(res_pre, ProjectionShortcut) and self._proj_in_kernel(x, chain):
+        elif isinstance(res_pre, ProjectionShortcut) and self._proj_in_kernel(x, chain, res_pre):
             proj, res_pre = (res_pre, False), None
         if isinstance(res_pre, ProjectionShortcut):
             res_pre = res_pre.tensor()
@@ -414,6 +442,19 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                 # xnor_half: the 16-bit result straight from the convolution's epilogue, with whatever fused_forward handed
                 # down (a plain forward hands nothing) -- the bits of the two lines below
                 join()
+                if proj is not None:
+                    # a 16-bit projection shortcut (resnet.PROJ_HALF) computed in this launch's residual registers, never
+                    # rounded on its own; refused: the shortcut as a 16-bit tensor in front (rounded there: other bits)
+                    sc, post = proj
+                    took, y16 = _hip.xnor_conv2d_proj_half(planes, k, scales, wbits, wsum, wscales, bias, geom,
+                                                           (sc.x.contiguous(), sc.w, sc.b, sc.stride, post), x.dtype, relu,
+                                                           res_pre, res_post, prelu)
+                    if took:
+                        return y16
+                    if post:
+                        res_post = sc.tensor()
+                    else:
+                        res_pre = sc.tensor()
                 return _hip.xnor_conv2d_half(planes, k, scales, wbits, wsum, wscales, bias, geom, x.dtype, relu, res_pre,
                                              res_post, prelu)
             _hip.xnor_conv2d(planes, k, scales, wbits, wsum, wscales, bias, geom, y)

@@ -127,7 +127,8 @@ class _Stem(nn.Sequential):
 
 class _ConvBN(nn.Sequential):
     """``Sequential(conv, bn)`` (same ``state_dict`` keys as the reference) that runs as ONE convolution
-    with the batch norm folded into its weights and bias in eval mode on the GPU."""
+    with the batch norm folded into its weights and bias in eval mode on the GPU: a strided 1x1 projection on
+    lsq_pointwise_conv for an fp32 input and, with ``PROJ_HALF``, on lsq_pointwise_conv_half for a bf16 / fp16 one."""
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         conv, bn = self[0], self[1]
@@ -139,6 +140,10 @@ class _ConvBN(nn.Sequential):
                         and max(x.numel(), x.numel() // conv.in_channels * conv.out_channels) < 2 ** 30):
                     # the strided gather happens while staging the GEMM operand (csrc/lsq_pointwise.hip)
                     return _hip.pointwise_conv(x, w.view(conv.out_channels, conv.in_channels), b, conv.stride[0])
+                if _proj_half_ok(conv, x, w):
+                    # PROJ_HALF: the same kernel reading the 16-bit samples as they are, fp32 folded weights, one rounding
+                    return _hip.pointwise_conv_half(x.detach().contiguous(), w.view(conv.out_channels, conv.in_channels), b,
+                                                    conv.stride[0])
                 return self._pointwise(x, w, b, conv.stride)
             return nn.functional.conv2d(x, w, b, conv.stride, conv.padding, conv.dilation, conv.groups)
         return bn(conv(x))
@@ -157,6 +162,25 @@ class _ConvBN(nn.Sequential):
         buf = hit[2]
         buf[:, :c].view(n, c, ho, wo).copy_(xs)
         return torch.matmul(hit[1], buf).view(n, -1, ho, wo)
+
+
+#: a bf16 / fp16 CUDA input of a folded 1x1 projection shortcut (fp32 folded weights, the shape conditions of the fp32 kernel
+#: branch, autocast off or set to the input's type) takes lsq_pointwise_conv_half, and where ``FUSE_PROJECTION`` and the consumer
+#: (``act_half`` and ``xnor_half`` set, two-plane activations) allow it the shortcut is computed inside lsq_xnor_conv2d_proj_half
+#: instead.  Each is bit for bit its fp32 kernel on the widened operands rounded once; unlike in fp32 the fused and the unfused
+#: route differ (the unfused one rounds the shortcut on its own).  False: the torch formulation, the default whatever the
+#: measurement says in the change that adds it
+PROJ_HALF = False
+
+
+def _proj_half_ok(conv: nn.Conv2d, x: torch.Tensor, w: torch.Tensor) -> bool:
+    """``PROJ_HALF`` and the conditions of the 16-bit projection kernels (``conv`` is a 1x1, unpadded, ungrouped convolution and
+    ``x`` a 4-d tensor already): a bf16 / fp16 CUDA ``x``, fp32 folded weights ``w``, the shape conditions of
+    ``_ConvBN.forward``'s fp32 branch, autocast off or set to ``x``'s type."""
+    return (PROJ_HALF and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and w.dtype == torch.float32
+            and conv.stride[0] == conv.stride[1] and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
+            and max(x.numel(), x.numel() // conv.in_channels * conv.out_channels) < 2 ** 30
+            and not (torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') != x.dtype))
 
 
 def _projection(in_planes: int, planes: int, stride: int, bias: bool) -> nn.Sequential:
@@ -252,16 +276,22 @@ FUSE_PROJECTION = True
 
 def _fused_projection(shortcut: nn.Module, x: torch.Tensor, consumer: QuantConv2d):
     """The ``ProjectionShortcut`` of a folded ``_ConvBN`` shortcut that the consumer's kernel can compute itself (the
-    conditions of ``_ConvBN.forward``'s kernel branch, two-plane binary activations, a shape the gate lists), else None."""
+    conditions of ``_ConvBN.forward``'s kernel branch, two-plane binary activations, a shape the gate lists), else None.
+    With ``PROJ_HALF`` also for a bf16 / fp16 ``x`` when the consumer has ``act_half`` and ``xnor_half`` set: its launch is then
+    lsq_xnor_conv2d_proj_half."""
     if not FUSE_PROJECTION or SIDE_STREAM_SHORTCUT or not isinstance(shortcut, _ConvBN):
         return None
     conv, bn = shortcut[0], shortcut[1]
     if not _eval_fold_ok(shortcut, bn, x) or consumer.x_quant not in ('ls-2', 'ls-T'):
         return None
-    if not (conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.groups == 1 and x.dim() == 4
-            and x.dtype == torch.float32 and conv.weight.dtype == torch.float32 and conv.stride[0] == conv.stride[1]
-            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
-            and max(x.numel(), x.numel() // conv.in_channels * conv.out_channels) < 2 ** 30):
+    if not (conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.groups == 1 and x.dim() == 4):
+        return None
+    if x.dtype == torch.float32:
+        if not (conv.weight.dtype == torch.float32 and conv.stride[0] == conv.stride[1]
+                and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
+                and max(x.numel(), x.numel() // conv.in_channels * conv.out_channels) < 2 ** 30):
+            return None
+    elif not (consumer.act_half and consumer.xnor_half and _proj_half_ok(conv, x, conv.weight)):
         return None
     if not _hip.proj_fused_wins(conv.in_channels, conv.out_channels):
         return None
