@@ -73,7 +73,8 @@ int lsq_signw_conv2d_half_plan(const lsq_conv_geom* g);
  *                rewritten by the call; where that is 0 it may be NULL (LSQ_E_WORKSPACE if it is NULL, misaligned or too
  *                small where one is needed)
  * No fused epilogue: no folded batch norm, ReLU / PReLU or residual operands -- on a 16-bit tensor torch rounds after each
- * of them, so they cannot be fused without changing bits.
+ * of them, so they cannot be fused without changing bits.  The call that fuses them and rounds once, with other bits than
+ * the composition in torch, is lsq_signw_conv2d_fused_half of lsq_hip_conv_fused_half.h; this one stays as it is.
  * Accuracy: every clamped activation is a value of x_dtype and the weights are exact +-1 in that type, so every product is
  * exact, and the products are summed in fp32 by v_mfma_f32_32x32x16_bf16 / v_mfma_f32_32x32x16_f16: ONE matrix instruction
  * per (16 channels, tap) and tile (lsq_signw_conv2d issues two, for the hi and the lo half of an fp32 value), one LDS plane,

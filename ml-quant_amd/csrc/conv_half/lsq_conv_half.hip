@@ -18,6 +18,7 @@
 
 #include "lsq_hip_conv_half.h"
 #include "../lsq_signw_conv_core.h"
+#include "lsq_conv_half_plan.h"      // host side: Plan, plan_of, workspace_bytes_of, fill_clamp
 
 namespace lsq {
 namespace signw {
@@ -52,54 +53,11 @@ struct X16 {
   typedef unsigned short T;            // an element of x in memory
   typedef unsigned Raw;                // ... in a register right after its load
   static constexpr bool kFp32 = false, kF16 = F16;
+  static constexpr bool kFused = false;
   static constexpr int kPlanes = 1, kPerReg = 2;
   template <bool PATCH>
   using Off = long long;
 };
-
-// ---- host side
-struct Plan {
-  int kind;                            // LSQ_CONV_HALF_* bits
-  int Ho, Wo;
-  PatchPlan pp;
-};
-
-bool half_type(int t) { return t == LSQ_DTYPE_BF16 || t == LSQ_DTYPE_F16; }
-
-// 0 and *p filled, or a negative LSQ_E_* code.  The patch rule is patch_plan, lsq_signw_conv2d's own, so that both libraries
-// take a patch kernel for the same geometries.
-int plan_of(const lsq_conv_geom* g, Plan* p) {
-  if (int e = check_geom(g)) return e;
-  const long long Hp = (long long)g->H + 2ll * g->pad_h, Wp = (long long)g->W + 2ll * g->pad_w;
-  const long long Ho64 = (Hp - (long long)g->dil_h * (g->KH - 1) - 1) / g->stride_h + 1;
-  const long long Wo64 = (Wp - (long long)g->dil_w * (g->KW - 1) - 1) / g->stride_w + 1;
-  if (Hp - (long long)g->dil_h * (g->KH - 1) - 1 < 0 || Wp - (long long)g->dil_w * (g->KW - 1) - 1 < 0) return LSQ_E_SHAPE;
-  const long long lim = 1ll << 31;
-  if (Hp >= lim || Wp >= lim || Ho64 >= lim || Wo64 >= lim) return LSQ_E_UNSUPPORTED;
-  // (products of at most three factors below 2^31 each: checked step by step)
-  auto prod_fits = [&](long long a, long long b, long long c, long long d) {
-    long long v = a;
-    for (long long f : {b, c, d}) {
-      if (v >= lim) return false;
-      v *= f;
-    }
-    return v < lim;
-  };
-  const int cg = g->C / g->groups, og = g->O / g->groups;
-  const long long Gg = (cg + 63) / 64, og_pad = (og + 15) / 16 * 16;
-  if (!prod_fits(g->N, g->C, g->H, g->W) || !prod_fits(g->N, g->O, Ho64, Wo64) || !prod_fits(g->N, Hp, Wp, 1)) return LSQ_E_UNSUPPORTED;
-  if (!prod_fits(g->KH, g->KW, Gg, (long long)g->groups * og_pad) ||
-      (long long)g->KH * g->KW * Gg * g->groups * og_pad >= (1ll << 28))
-    return LSQ_E_UNSUPPORTED;
-  const int og_tiles = (og + tile_bm(og > 64) - 1) / tile_bm(og > 64);
-  if ((long long)g->groups * og_tiles > 65535) return LSQ_E_UNSUPPORTED;
-  p->Ho = (int)Ho64; p->Wo = (int)Wo64;
-  p->pp = patch_plan(g, Ho64, Wo64, false);
-  p->kind = p->pp.wide ? LSQ_CONV_HALF_WIDE : 0;
-  if (p->pp.patch)
-    p->kind |= LSQ_CONV_HALF_PATCH | (p->pp.unit ? LSQ_CONV_HALF_UNIT_STRIDE : 0) | (p->pp.many ? LSQ_CONV_HALF_MANY_TAPS : 0);
-  return LSQ_OK;
-}
 
 }  // namespace
 }  // namespace signw
@@ -116,11 +74,8 @@ extern "C" int lsq_signw_conv2d_half_plan(const lsq_conv_geom* g) {
   return p.kind;
 }
 
-// A launch holds one plane: the fp32 running sum of a 16-bit y of more than one plane lives in the workspace.
 extern "C" int64_t lsq_signw_conv2d_half_workspace_bytes(const lsq_conv_geom* g, int kw_planes, int y_dtype) {
-  Plan p;
-  if (!half_type(y_dtype) || kw_planes <= 1 || plan_of(g, &p)) return 0;
-  return 4ll * g->N * g->O * p.Ho * p.Wo;
+  return workspace_bytes_of(g, kw_planes, y_dtype);
 }
 
 extern "C" int lsq_signw_conv2d_half(const void* x, int x_dtype, float clamp_alpha, const uint64_t* wbits, int kw_planes,
@@ -138,15 +93,7 @@ extern "C" int lsq_signw_conv2d_half(const void* x, int x_dtype, float clamp_alp
   HArgs a = {};
   a.x = static_cast<const unsigned short*>(x);
   a.bias = bias;
-  // the bound is used as given: the caller has rounded it into the activations' type (a NaN or negative one: identity)
-  a.lim = clamp_alpha >= 0.f ? clamp_alpha : INFINITY;
-  a.clamp = !isinf(a.lim);
-  {
-    const _Float16 h = (_Float16)a.lim;
-    uint16_t hb;
-    memcpy(&hb, &h, 2);
-    a.lim2 = (uint32_t)hb << 16 | hb;
-  }
+  fill_clamp(a, clamp_alpha);
   fill_geom(a, g, p.Ho, p.Wo);
   const long long wplane_words = (long long)g->KH * g->KW * a.Gg * a.opad_total;
   float* const sum = need ? static_cast<float*>(workspace) : static_cast<float*>(y);   // the fp32 sum between launches

@@ -23,6 +23,7 @@ struct XF32 {
   typedef float T;                     // an element of x in memory
   typedef float Raw;                   // ... in a register right after its load
   static constexpr bool kFp32 = true, kF16 = false;
+  static constexpr bool kFused = false;
   static constexpr int kPlanes = 2, kPerReg = 1;
   template <bool PATCH>
   using Off = std::conditional_t<PATCH, unsigned, size_t>;

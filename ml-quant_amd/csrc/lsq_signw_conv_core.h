@@ -21,6 +21,10 @@
 //   T, Raw          an element of x in memory / in a register right after its load (float, float / unsigned short, unsigned)
 //   kFp32           fp32 activations: folded batch norm, clamp, bf16 hi / lo split, fused epilogue; else 16-bit words clamped
 //                   in their own type and Args::store(index, value) in the epilogue
+//   kFused          16-bit only (the fused library's X16F / HFArgs, conv_fused_half/): a folded batch norm in the read --
+//                   fold2 on the scales and shifts of the chunk being staged, read at wave-uniform addresses, no table in
+//                   LDS, so the plan does not depend on it -- and the fp32 epilogue act(out + res_pre) + res_post on 16-bit
+//                   residuals before Args::store
 //   kF16            the MFMA's operand type (16-bit only: fp16, else bf16)
 //   kPlanes         LDS planes per patch or chunk: 2 (hi + lo) or 1;  kPerReg: activations per staged register, 1 or 2
 //   Off<PATCH>      type of the epilogue's output offsets in conv_patch / conv_tiled
@@ -29,7 +33,7 @@
 // behind functions of X: a function is simplified on its own before it is inlined, and every such helper tried (conversion
 // with the validity flag as a parameter, an epilogue object, an MFMA step looping over planes) changed the schedule of the
 // kernels that used it.  As written, 28 of the 30 kernels are instruction for instruction what the two files held before
-// (DESIGN 4.23).
+// (DESIGN 4.23); the kFused branches left all 30 as they were.
 #pragma once
 
 #include "lsq_signw_conv.h"
@@ -76,12 +80,36 @@ __device__ __forceinline__ unsigned clamp2(unsigned d, const A& a) {
   }
 }
 
+// kFused: two 16-bit activations of channels with folded batch norms (s0, b0), (s1, b1) -> fl32(fl32(v * s) + b), a separate
+// multiply and add, rounded to nearest even into the type (v_cvt_pk_bf16_f32 / v_cvt_f16_f32: fp16 overflow gives +-inf),
+// packed as they came.  The rule of lsq_act_quant_bn_half.
+template <bool F16>
+__device__ __forceinline__ unsigned fold2(unsigned lo, unsigned hi, float s0, float b0, float s1, float b1) {
+  if constexpr (F16) {
+    const float t0 = (float)__builtin_bit_cast(_Float16, (unsigned short)lo) * s0 + b0;
+    const float t1 = (float)__builtin_bit_cast(_Float16, (unsigned short)hi) * s1 + b1;
+    const f16x2 h = {(_Float16)t0, (_Float16)t1};
+    return __builtin_bit_cast(unsigned, h);
+  } else {
+    const f32x2 t = {__builtin_bit_cast(float, lo << 16) * s0 + b0, __builtin_bit_cast(float, hi << 16) * s1 + b1};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(t, bf16x2));
+  }
+}
+
+// a 16-bit residual element as fp32 (kFused)
+template <bool F16>
+__device__ __forceinline__ float half_to_f32(unsigned short h) {
+  if constexpr (F16) return (float)__builtin_bit_cast(_Float16, h);
+  else return __builtin_bit_cast(float, (unsigned)h << 16);
+}
+
 // Epilogue of both kernels: lane = pixel column, registers = out-channel rows (coalesced stores: consecutive elements of a
 // row per half-wave); out = base + acc * ws[o] with a separate multiply and add, base = bias[o] (or 0) at the first plane
 // and the fp32 sum of the planes before it afterwards.
 //   fp32:   y = relu(out + res_pre) + res_post on the last weight plane, a float store.  Off = byte offsets: unsigned when
 //           the host has checked 4*N*O*Ho*Wo < 2^32 (one vector add per output address: conv_patch), else size_t.
-//   16-bit: Args::store.  Off = long long element indices.
+//   16-bit: Args::store.  Off = long long element indices.  kFused: the fp32 epilogue in front of it on the last plane, the
+//           residuals one 16-bit element per load at the output's own index.
 template <class X, typename Off, int BM, int BN, int TM, int TN>
 __device__ __forceinline__ void store_tiles(const typename X::Args& a, const f32x16 (&acc)[TM][TN], int ptile, int t, int o0,
                                             int wm, int wn, int col, int kh8) {
@@ -107,6 +135,14 @@ __device__ __forceinline__ void store_tiles(const typename X::Args& a, const f32
     rpost = reinterpret_cast<const char*>(a.res_post);
     want_pre = a.final_pass && a.res_pre, want_post = a.final_pass && a.res_post;
   }
+  // kFused: the residual loads are issued unconditionally -- an absent operand reads element 0 of x, a valid address, and is
+  // not added --, so that no load stands inside a branch (conv_tiled's load_chunk says why)
+  [[maybe_unused]] const unsigned short *hpre = nullptr, *hpost = nullptr;
+  if constexpr (X::kFused) {
+    want_pre = a.final_pass && a.res_pre, want_post = a.final_pass && a.res_post;
+    hpre = want_pre ? a.res_pre : a.x;
+    hpost = want_post ? a.res_post : a.x;
+  }
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -115,7 +151,7 @@ __device__ __forceinline__ void store_tiles(const typename X::Args& a, const f32
       // residuals, scale, bias) is issued before the first use -- a load consumed right after it is issued
       // costs one memory latency per output
       float ws[8], bs[8], prev[8][TN];
-      [[maybe_unused]] float sl[8], r1[8][TN], r2[8][TN];                 // fp32 only
+      [[maybe_unused]] float sl[8], r1[8][TN], r2[8][TN];                 // fp32 and kFused only
       Off yo[8][TN];
       bool ok[8][TN];
 #pragma unroll
@@ -137,6 +173,17 @@ __device__ __forceinline__ void store_tiles(const typename X::Args& a, const f32
             prev[qq][j] = a.accumulate ? *reinterpret_cast<const float*>(yb + yo[qq][j]) : 0.f;
             r1[qq][j] = want_pre ? *reinterpret_cast<const float*>(rpre + yo[qq][j]) : 0.f;
             r2[qq][j] = want_post ? *reinterpret_cast<const float*>(rpost + yo[qq][j]) : 0.f;
+          }
+        } else if constexpr (X::kFused) {
+          bs[qq] = (!a.prev && a.bias) ? a.bias[o] : 0.f;
+          sl[qq] = (a.final_pass && a.act >= LSQ_ACT_PRELU) ? a.slope[a.act == LSQ_ACT_PRELU ? 0 : o] : 0.f;
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            ok[qq][j] = rok && pok[j];
+            yo[qq][j] = ok[qq][j] ? pbase[j] + (long long)olu * HoWo : 0ll;
+            prev[qq][j] = a.prev ? a.prev[yo[qq][j]] : 0.f;
+            r1[qq][j] = half_to_f32<X::kF16>(hpre[want_pre ? yo[qq][j] : 0ll]);
+            r2[qq][j] = half_to_f32<X::kF16>(hpost[want_post ? yo[qq][j] : 0ll]);
           }
         } else {
           bs[qq] = (!a.prev && a.bias) ? a.bias[o] : 0.f;
@@ -161,6 +208,15 @@ __device__ __forceinline__ void store_tiles(const typename X::Args& a, const f32
               out += r2[qq][j];
             }
             if (ok[qq][j]) *reinterpret_cast<float*>(yb + yo[qq][j]) = out;
+          } else if constexpr (X::kFused) {
+            float out = (a.prev ? prev[qq][j] : bs[qq]) + acc[i][j][qh * 8 + qq] * ws[qq];
+            if (a.final_pass) {              // (an absent operand adds nothing: a -0 sum stays -0, as in the unfused call)
+              if (want_pre) out += r1[qq][j];
+              if (a.act == LSQ_ACT_RELU) out = fmaxf(out, 0.f);
+              else if (a.act >= LSQ_ACT_PRELU) out = out > 0.f ? out : sl[qq] * out;
+              if (want_post) out += r2[qq][j];
+            }
+            if (ok[qq][j]) a.store(yo[qq][j], out);
           } else {
             const float out = (a.prev ? prev[qq][j] : bs[qq]) + acc[i][j][qh * 8 + qq] * ws[qq];
             if (ok[qq][j]) a.store(yo[qq][j], out);
@@ -258,6 +314,26 @@ __global__ __launch_bounds__(256) void conv_tiled(typename X::Args a) {
         }
         v = clamp_sym(v, a.alpha);
         xr[j] = (inb && c < a.cg) ? v : 0.f;
+      }
+    } else if constexpr (X::kFused) {
+      // the folded batch norm of the 16 channels being staged: the channel is the same for all lanes of a wave (k half =
+      // tid >> 7), scalar loads; the padding is of the folded value: zeroed after the fold
+      float ps[16], pb[16];
+      if (a.pre_scale) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int cs = __builtin_amdgcn_readfirstlane(grp * a.cg + min(cbase + j, a.cg - 1));
+          ps[j] = a.pre_scale[cs];
+          pb[j] = a.pre_shift[cs];
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < 8; ++p) {
+        const unsigned d = a.pre_scale ? fold2<X::kF16>(raw[2 * p], raw[2 * p + 1], ps[2 * p], pb[2 * p], ps[2 * p + 1], pb[2 * p + 1])
+                                       : raw[2 * p] | raw[2 * p + 1] << 16;
+        const unsigned lo = (inb && cbase + 2 * p < a.cg) ? d & 0xFFFFu : 0u;
+        const unsigned hi16 = (inb && cbase + 2 * p + 1 < a.cg) ? d & 0xFFFF0000u : 0u;
+        xr[p] = clamp2<X::kF16>(lo | hi16, a);
       }
     } else {
 #pragma unroll
@@ -518,6 +594,26 @@ __global__ __launch_bounds__(256) void conv_patch(typename X::Args a, int Hp, in
           const int dst = it_dst[u] & 0xFFFFF;
           *reinterpret_cast<uint4*>(sP + dst) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
           *reinterpret_cast<uint4*>(sP + kPlane + dst) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+        } else if constexpr (X::kFused) {                // folded batch norm of this octet's channels, then as below
+          float ps[8], pb[8];
+          if (a.pre_scale) {                             // wave-uniform addresses: scalar loads
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const int cs = __builtin_amdgcn_readfirstlane(grp * a.cg + min(c0 + j, a.cg - 1));
+              ps[j] = a.pre_scale[cs];
+              pb[j] = a.pre_shift[cs];
+            }
+          }
+          unsigned d[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const unsigned f = a.pre_scale ? fold2<X::kF16>(raw[u][2 * q], raw[u][2 * q + 1], ps[2 * q], pb[2 * q], ps[2 * q + 1], pb[2 * q + 1])
+                                           : raw[u][2 * q] | raw[u][2 * q + 1] << 16;
+            const unsigned lo = (it_off[u] >= 0 && (!ragged || c0 + 2 * q < a.cg)) ? f & 0xFFFFu : 0u;
+            const unsigned hi16 = (it_off[u] >= 0 && (!ragged || c0 + 2 * q + 1 < a.cg)) ? f & 0xFFFF0000u : 0u;
+            d[q] = clamp2<X::kF16>(lo | hi16, a);
+          }
+          *reinterpret_cast<uint4*>(sP + (it_dst[u] & 0xFFFFF)) = make_uint4(d[0], d[1], d[2], d[3]);
         } else {                                         // clamp in the activations' own type
           unsigned d[4];
 #pragma unroll

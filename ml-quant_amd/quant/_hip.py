@@ -647,6 +647,7 @@ train_half_lib, train_half_library_path, TRAIN_HALF_ABI_VERSION = _sublib('train
 linear_wgrad_half_lib, linear_wgrad_half_library_path, LINEAR_WGRAD_HALF_ABI_VERSION = _sublib('linear_wgrad_half')
 conv_act_bn_half_lib, conv_act_bn_half_library_path, CONV_ACT_BN_HALF_ABI_VERSION = _sublib('conv_act_bn_half')
 conv_proj_half_lib, conv_proj_half_library_path, CONV_PROJ_HALF_ABI_VERSION = _sublib('conv_proj_half')
+conv_fused_half_lib, conv_fused_half_library_path, CONV_FUSED_HALF_ABI_VERSION = _sublib('conv_fused_half')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1174,6 +1175,82 @@ def signw_conv2d_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscale
                          f'C{C}_H{H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
         check(hl.lsq_signw_conv2d_half(x.data_ptr(), xdt, float(alpha), wbits.data_ptr(), kw, wscales.data_ptr(), ptr(bias),
                                        ctypes.byref(geom), y.data_ptr(), ydt, *_ws_args(ws), stream_ptr(dev)), what)
+    return y
+
+
+# ---- the same convolution with the folded batch norm in its read and the block epilogue in the launch
+# (include/lsq_hip_conv_fused_half.h)
+def signw_conv2d_fused_half(x: torch.Tensor, alpha: float, wbits: torch.Tensor, wscales: torch.Tensor,
+                            bias: Optional[torch.Tensor], geom: ConvGeom, pre: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                            relu: bool = False, res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
+                            prelu: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """y [N, O, Ho, Wo] = act(conv(t.clamp(-alpha, alpha), w_q) + bias + res_pre) + res_post in one launch per weight plane
+    (lsq_signw_conv2d_fused_half): the operands of ``signw_conv2d_half`` and
+      * ``pre = (scale, shift)``, fp32 contiguous tensors of C elements, the folded batch norm:
+        ``t = (x.float() * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)).to(x.dtype)``, never in memory; ``None``: t = x;
+      * ``relu`` / ``prelu`` (an nn.PReLU weight of 1 or O fp32 slopes), exclusive;
+      * ``res_pre`` / ``res_post``: tensors of x's type and y's shape, read as they are.
+    The result has the values of ``signw_conv2d_half(t, ..., out_dtype=torch.float32)`` followed by the epilogue in fp32,
+    rounded once into ``out_dtype`` (x.dtype, the default, or torch.float32).  The fp32 running sum of a 16-bit result of more
+    than one plane lives in a workspace cached per (device, stream), as ``signw_conv2d_half``'s does."""
+    what = 'lsq_signw_conv2d_fused_half'
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    _check_half(what, 'x', x)
+    if out_dtype not in (torch.float32, x.dtype):
+        raise TypeError(f'{what}: out_dtype must be torch.float32 or {x.dtype}, got {out_dtype}')
+    res = {name: t for name, t in (('res_pre', res_pre), ('res_post', res_post)) if t is not None}
+    wrong = [name for name, t in res.items() if t.dtype != x.dtype]
+    if wrong:
+        raise TypeError(f'{what}: {", ".join(wrong)} must be {x.dtype} tensors')
+    named = {'wscales': wscales}
+    if bias is not None:
+        named['bias'] = bias
+    if pre is not None:
+        named['pre_scale'], named['pre_shift'] = pre
+    if prelu is not None:
+        named['prelu'] = prelu
+    fp32 = _check_dtypes(what, named)
+    if wbits.dtype != torch.int64:
+        raise TypeError(f'{what}: wbits must be a torch.int64 tensor')
+    ho, wo = out_hw(geom)
+    shape = (geom.N, geom.O, ho, wo)
+
+    def problem():
+        if x.dim() != 4 or x.numel() == 0 or wscales.dim() != 2 or wscales.shape[0] < 1:
+            return f'bad sizes: x of shape {tuple(x.shape)}, wscales of shape {tuple(wscales.shape)}'
+        if (geom.N, geom.C, geom.H, geom.W) != tuple(x.shape) or min(geom.O, geom.KH, geom.KW, geom.groups) < 1 \
+                or geom.C % geom.groups or geom.O % geom.groups:
+            return f'the geometry and x of shape {tuple(x.shape)} do not match'
+        if wscales.shape[1] != geom.O or wbits.numel() < wscales.shape[0] * _signw_plane_words(geom) \
+                or (bias is not None and tuple(bias.shape) != (geom.O,)):
+            return 'weight planes / scales / bias and (kw, geometry) do not match'
+        if pre is not None and (pre[0].numel() != geom.C or pre[1].numel() != geom.C):
+            return f'pre_scale / pre_shift and the {geom.C} channels of x do not match'
+        if prelu is not None and (relu or prelu.numel() not in (1, geom.O)):
+            return f'prelu of {prelu.numel()} slopes on {geom.O} channels' + (' together with relu' if relu else '')
+        for name, t in res.items():
+            if tuple(t.shape) != shape:
+                return f'{name} of shape {tuple(t.shape)} must have the shape of y, {shape}'
+
+    _check_placement(what, [x, wbits, *res.values(), *fp32], problem)
+    if ho < 1 or wo < 1:
+        raise ValueError(f'{what}: the geometry has an empty output')
+    act, slope = _act(relu, None if prelu is None else prelu.detach(), geom.O)
+    (N, C, H, W), kw, dev = x.shape, wscales.shape[0], x.device
+    fl = conv_fused_half_lib()
+    xdt, ydt = LINEAR_HALF_DTYPES[x.dtype], LINEAR_HALF_DTYPES[out_dtype]
+    need = int(fl.lsq_signw_conv2d_fused_half_workspace_bytes(ctypes.byref(geom), kw, ydt))
+    ws = _stream_buffer('conv_fused_half', need, dev) if need else None
+    y = torch.empty(shape, dtype=out_dtype, device=dev)
+    # algorithmic bytes: x read per plane + the fp32 sum written and read back per plane before the last + every 16-bit
+    # residual read + y written
+    nbytes = 2 * x.numel() * kw + 8 * y.numel() * (kw - 1) + 2 * y.numel() * len(res) + y.element_size() * y.numel()
+    with _on(y), (_Timed(what, nbytes, 2 * y.numel() * (C // geom.groups) * geom.KH * geom.KW * kw,
+                         f'C{C}_H{H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
+        check(fl.lsq_signw_conv2d_fused_half(
+            x.data_ptr(), xdt, float(alpha), None if pre is None else pre[0].data_ptr(), None if pre is None else pre[1].data_ptr(),
+            wbits.data_ptr(), kw, wscales.data_ptr(), ptr(bias), ctypes.byref(geom), act, ptr(slope), ptr(res_pre), ptr(res_post),
+            y.data_ptr(), ydt, *_ws_args(ws), stream_ptr(dev)), what)
     return y
 
 

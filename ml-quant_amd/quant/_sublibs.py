@@ -150,6 +150,10 @@ SUBLIBS = (
         'lsq_pointwise_conv_half': (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
         'lsq_xnor_conv2d_proj_half': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, ctypes.POINTER(ProjHalf),
                                             i32, vp, vp])}),
+    _entry('conv_fused_half', '|lsq_signw_conv2d_fused_half[a-z0-9_]*', {
+        'lsq_signw_conv2d_fused_half_plan': (i32, [vp]),
+        'lsq_signw_conv2d_fused_half_workspace_bytes': (i64, [vp, i32, i32]),
+        'lsq_signw_conv2d_fused_half': (i32, [vp, i32, f32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, sz, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

@@ -38,6 +38,10 @@ Dispatch of ``forward``:
   * with ``act_half_bn_fold`` set on top of ``act_half`` (class attribute, False by default): ``fused_forward`` folds an
     eval-mode ``pre_bn`` of a 16-bit input into the quantizer's read, lsq_act_quant_bn_half
     (liblsq_hip_conv_act_bn_half.so), instead of running it in torch (DESIGN 4.30);
+  * with ``fp_half_fused`` set on top of ``fp_half`` (class attribute, False by default): ``fused_forward`` on a 16-bit input
+    with ``fp`` activations hands non-linearity and 16-bit residuals to ONE lsq_signw_conv2d_fused_half
+    (liblsq_hip_conv_fused_half.so), which rounds once; with ``fp_half_bn_fold`` on top of it an eval-mode ``pre_bn`` goes
+    into that launch's read too instead of running in torch (DESIGN 4.32);
   * anything else (CPU tensors, grouped / dilated training convolutions, 16-bit inputs with binary activations without
     ``act_half`` or with ``fp`` activations without ``fp_half``, 16-bit weights, an autocast of another type) -> the torch
     formulation in ``quant.binary``.
@@ -142,6 +146,20 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: norm but not its bits.  A switch of its own; False: torch's batch norm in front of lsq_act_quant_half, the default
     #: whatever the measurement says in the change that adds it
     act_half_bn_fold = False
+
+    #: with ``fp_half`` and ``fp_half_kernel``: ``fused_forward`` on a bf16 / fp16 CUDA input with ``fp`` activations runs the
+    #: batch norm in torch in front (if any) and then ONE lsq_signw_conv2d_fused_half, which adds ``res_pre``, applies ReLU /
+    #: PReLU and adds ``res_post`` in fp32 and rounds once, where the composition in torch rounds after every step: other
+    #: bits, within the roundings it saves.  Residuals of another type or shape take the composition.  A switch of its own;
+    #: False: the composition around lsq_signw_conv2d_half, the default whatever the measurement says in the change that adds
+    #: it
+    fp_half_fused = False
+
+    #: with ``fp_half_fused``: an eval-mode ``pre_bn`` (running statistics, on x's device) is not run in torch but handed to
+    #: that launch as its folded (scale, shift): the layer on ``(x.float() * scale + shift).to(x.dtype)``, within one rounding
+    #: of the type of torch's own batch norm but not its bits.  A train-mode batch norm keeps the whole composition, as with
+    #: both switches off.  False by default
+    fp_half_bn_fold = False
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
@@ -271,6 +289,20 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                 xin = x if pre_bn is None else pre_bn(x)
                 if self._wants_hip(xin) and self._half_epilogue_fits(xin, res_pre, res_post, prelu):
                     return self._forward_hip(xin, None, relu, res_pre, res_post, prelu, None, res_ready)
+        if self._fuses_fp_half(x, pre_bn) and self._half_epilogue_fits(x, res_pre, res_post, prelu):
+            # a 16-bit input with fp activations and ``fp_half_fused``: the batch norm in torch in front (with
+            # ``fp_half_bn_fold`` in the launch's read), then non-linearity and 16-bit residuals in the epilogue of
+            # lsq_signw_conv2d_fused_half -- one launch, one rounding.  A ProjectionShortcut of x's type is its tensor first.
+            pre = self._folded_bn(pre_bn) if pre_bn is not None and self._folds_fp_half_bn(x, pre_bn) else None
+            # (an eval-mode batch norm that runs here runs ONCE: should its result be of another type, the composition below
+            # takes ``xin`` as it is instead of calling ``pre_bn`` again; a train-mode one never gets here)
+            xin = x if pre_bn is None or pre is not None else pre_bn(x)
+            if xin.dtype == x.dtype and xin.shape == x.shape:
+                if isinstance(res_pre, ProjectionShortcut):
+                    res_pre = res_pre.tensor()
+                if isinstance(res_post, ProjectionShortcut):
+                    res_post = res_post.tensor()
+                return self._forward_fp_half_fused(xin, pre, relu, res_pre, res_post, prelu, res_ready)
         if (x.dtype == torch.float32 and self._wants_hip(x)
                 and (pre_bn is None or (not pre_bn.training and pre_bn.track_running_stats))):
             # next_q = (batch norm or None, QuantConv2d) that will consume the result: with 1-bit activations on both
@@ -306,8 +338,40 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                 and x.dtype in (torch.bfloat16, torch.float16) and not bn.training and bn.track_running_stats
                 and bn.running_mean is not None and bn.running_mean.device == x.device and self._wants_hip(x))
 
+    def _fuses_fp_half(self, x: torch.Tensor, pre_bn: Optional[nn.BatchNorm2d] = None) -> bool:
+        """Whether ``fused_forward`` hands its epilogue to lsq_signw_conv2d_fused_half (``fp_half_fused``): a bf16 / fp16 CUDA
+        input with ``fp`` activations that this layer takes on lsq_signw_conv2d_half (``fp_half``, not the cast comparator;
+        eval mode and the rest of ``_wants_hip``), and no train-mode batch norm in front (that one keeps the composition as it
+        is: autograd and the running statistics are torch's).  The operands must pass ``_half_epilogue_fits`` besides."""
+        return (self.fp_half_fused and self.fp_half and self.fp_half_kernel and self.x_quant == 'fp' and x.is_cuda
+                and x.dtype in (torch.bfloat16, torch.float16) and (pre_bn is None or not pre_bn.training) and self._wants_hip(x))
+
+    def _folds_fp_half_bn(self, x: torch.Tensor, bn: nn.BatchNorm2d) -> bool:
+        """Whether that launch reads through ``bn`` (``fp_half_bn_fold``): the conditions of ``_folds_half_bn`` on the
+        ``fp`` side -- an eval-mode batch norm with running statistics on x's device."""
+        return (self.fp_half_bn_fold and self._fuses_fp_half(x, bn) and not bn.training and bn.track_running_stats
+                and bn.running_mean is not None and bn.running_mean.device == x.device)
+
+    def _forward_fp_half_fused(self, x: torch.Tensor, pre, relu: bool, res_pre: Optional[torch.Tensor],
+                               res_post: Optional[torch.Tensor], prelu: Optional[torch.Tensor],
+                               res_ready: Optional[torch.cuda.Event]) -> torch.Tensor:
+        """One lsq_signw_conv2d_fused_half: the route of ``_forward_hip`` for a 16-bit input with fp activations, with the
+        folded batch norm ``pre`` (or None) and the epilogue's operands handed down."""
+        from quant import _hip
+        x = x.detach().contiguous()
+        geom = self._geom_of(x, _hip)
+        wbits, _, wscales, _ = self._packed_weights(geom, _hip, prep=False)
+        res_pre = None if res_pre is None else res_pre.detach().contiguous()
+        res_post = None if res_post is None else res_post.detach().contiguous()
+        bias = None if self.bias is None else self.bias.detach()
+        if res_ready is not None:        # residual operands from a side stream: in front of the convolution
+            torch.cuda.current_stream(x.device).wait_event(res_ready)
+        return _hip.signw_conv2d_fused_half(x, self._alpha_in(x.dtype), wbits, wscales, bias, geom, pre, relu, res_pre, res_post,
+                                            prelu)
+
     def _half_epilogue_fits(self, x: torch.Tensor, res_pre, res_post, prelu) -> bool:
-        """Whether lsq_xnor_conv2d_half's epilogue takes these operands: residuals that are CUDA tensors of the input's type
+        """Whether lsq_xnor_conv2d_half's epilogue (and lsq_signw_conv2d_fused_half's, which takes a ``ProjectionShortcut`` as
+        its tensor) takes these operands: residuals that are CUDA tensors of the input's type
         and the output's shape, PReLU slopes in fp32 (1 or one per out-channel).  At most one of the residuals may be a
         ``ProjectionShortcut`` whose ``x`` is such a tensor and whose result has the output's shape (lsq_xnor_conv2d_proj_half,
         or lsq_pointwise_conv_half in front where that call is refused)."""
