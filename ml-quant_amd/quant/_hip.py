@@ -648,6 +648,7 @@ linear_wgrad_half_lib, linear_wgrad_half_library_path, LINEAR_WGRAD_HALF_ABI_VER
 conv_act_bn_half_lib, conv_act_bn_half_library_path, CONV_ACT_BN_HALF_ABI_VERSION = _sublib('conv_act_bn_half')
 conv_proj_half_lib, conv_proj_half_library_path, CONV_PROJ_HALF_ABI_VERSION = _sublib('conv_proj_half')
 conv_fused_half_lib, conv_fused_half_library_path, CONV_FUSED_HALF_ABI_VERSION = _sublib('conv_fused_half')
+bn_train_lib, bn_train_library_path, BN_TRAIN_ABI_VERSION = _sublib('bn_train')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1567,6 +1568,109 @@ def wgrad_half(planes: torch.Tensor, kx: int, xscales: torch.Tensor, gy: torch.T
         check(tl.lsq_train_wgrad_half(planes.data_ptr(), kx, xscales.data_ptr(), gy.data_ptr(), LINEAR_HALF_DTYPES[gy.dtype],
                                       ctypes.byref(geom), gwq.data_ptr(), ptr(gb), *_ws_args(ws), stream_ptr(dev)), what)
     return gwq, gb
+
+
+# ---- the train-mode batch norm in front of a quantized convolution (include/lsq_hip_bn_train.h)
+BN_TRAIN_MAX = 65535          # lsq_bn_train_*: N, C <= 65535
+
+
+def _check_bn(what: str, x: torch.Tensor, vectors: dict, like: Optional[dict] = None, scales: Optional[torch.Tensor] = None,
+              k: int = 0) -> tuple:
+    """The operand checks of the bn_train entry points: fp32, contiguous, a 4-d ``x`` within the limits, ``vectors`` of C elements
+    (None entries are optional operands left out), ``like`` of x's shape, plane scales [k, N]; returns (N, C, H, W)."""
+    vectors = {name: t for name, t in vectors.items() if t is not None}
+    fp32 = dict({'x': x}, **vectors, **(like or {}), **({} if scales is None else {'xscales': scales}))
+
+    def problem():
+        if x.dim() != 4 or x.numel() == 0 or not 0 <= k <= MAX_PLANES:
+            return f'bad sizes: x of shape {tuple(x.shape)}, k={k}'
+        if x.shape[0] > BN_TRAIN_MAX or x.shape[1] > BN_TRAIN_MAX:
+            return f'N, C <= {BN_TRAIN_MAX}: x of shape {tuple(x.shape)}'
+        wrong = [name for name, t in vectors.items() if t.numel() != x.shape[1]]
+        if wrong:
+            return f'{", ".join(wrong)} must have C = {x.shape[1]} elements'
+        wrong = [name for name, t in (like or {}).items() if t.shape != x.shape]
+        if wrong:
+            return f'{", ".join(wrong)} must have the shape of x'
+        if (k > 0) != (scales is not None) or (scales is not None and tuple(scales.shape) != (k, x.shape[0])):
+            return 'plane scales must be [k, N]'
+
+    _check_operands(what, fp32, problem=problem)
+    return tuple(x.shape)
+
+
+def bn_train_slabs(n: int, c: int, h: int, w: int) -> int:
+    """Slabs of samples per channel in the two reductions of this library for x [n, c, h, w] (from the workspace size: one
+    fp64 pair per channel and slab)."""
+    return int(bn_train_lib().lsq_bn_train_workspace_bytes(n, c, h, w)) // (16 * c)
+
+
+def bn_train_stats(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float,
+                   momentum: Optional[float], running_mean: Optional[torch.Tensor] = None,
+                   running_var: Optional[torch.Tensor] = None, batch_count: int = 1):
+    """(mean, var, invstd, scale, shift), each [C] fp32, of the train-mode batch norm of x [N, C, H, W] (lsq_bn_train_stats): the
+    batch mean and biased variance, 1 / sqrt(var + eps), scale = gamma invstd and shift = beta - mean scale.  ``running_mean`` /
+    ``running_var`` are updated in place as nn.BatchNorm2d does (``momentum`` None: the cumulative average over ``batch_count``
+    batches, this one included).  x is read once; the per-slab partial sums live in a workspace cached per (device, stream)."""
+    what = 'lsq_bn_train_stats'
+    n, c, h, w = _check_bn(what, x, {'gamma': gamma, 'beta': beta, 'running_mean': running_mean, 'running_var': running_var})
+    if (running_mean is None) != (running_var is None):
+        raise ValueError(f'{what}: running_mean and running_var come together')
+    if n * h * w < 2:
+        raise ValueError(f'{what}: expected more than 1 value per channel, got x of shape {tuple(x.shape)}')
+    bl = bn_train_lib()
+    out = torch.empty((5, c), dtype=torch.float32, device=x.device)
+    ws = _stream_buffer('bn_train', int(bl.lsq_bn_train_workspace_bytes(n, c, h, w)), x.device)
+    with _on(x), (_Timed(what, 4 * x.numel(), 0, f'C{c}_H{h}') if _timing is not None else _UNTIMED):
+        check(bl.lsq_bn_train_stats(x.data_ptr(), n, c, h, w, ptr(gamma), ptr(beta), float(eps),
+                                    -1.0 if momentum is None else float(momentum), int(batch_count), ptr(running_mean),
+                                    ptr(running_var), *(out[i].data_ptr() for i in range(5)), *_ws_args(ws),
+                                    stream_ptr(x.device)), what)
+    return out[0], out[1], out[2], out[3], out[4]
+
+
+def bn_apply(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
+    """y = fmaf(x, scale[c], shift[c]) (lsq_bn_apply): the tensor the quantizers see behind ``pre=(scale, shift)``."""
+    what = 'lsq_bn_apply'
+    n, c, h, w = _check_bn(what, x, {'scale': scale, 'shift': shift})
+    y = torch.empty_like(x)
+    with _on(x), (_Timed(what, 8 * x.numel(), 0, f'C{c}_H{h}') if _timing is not None else _UNTIMED):
+        check(bn_train_lib().lsq_bn_apply(x.data_ptr(), n, c, h, w, scale.data_ptr(), shift.data_ptr(), y.data_ptr(),
+                                          stream_ptr(x.device)), what)
+    return y
+
+
+def quant_values_bn(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, scales: Optional[torch.Tensor],
+                    alpha: float) -> torch.Tensor:
+    """``quant_values(bn_apply(x, scale, shift), scales, alpha)`` in one pass, bit for bit (lsq_quant_values_bn)."""
+    what = 'lsq_quant_values_bn'
+    k = 0 if scales is None else int(scales.shape[0])
+    n, c, h, w = _check_bn(what, x, {'scale': scale, 'shift': shift}, scales=scales, k=k)
+    out = torch.empty_like(x)
+    with _on(x), (_Timed(what, 8 * x.numel(), 0, f'C{c}_H{h}') if _timing is not None else _UNTIMED):
+        check(bn_train_lib().lsq_quant_values_bn(x.data_ptr(), n, c, h, w, scale.data_ptr(), shift.data_ptr(), k, ptr(scales),
+                                                 float(alpha), out.data_ptr(), stream_ptr(x.device)), what)
+    return out
+
+
+def bn_ste_backward(x: torch.Tensor, grad_q: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, mean: torch.Tensor,
+                    invstd: torch.Tensor, scales: Optional[torch.Tensor], alpha: float):
+    """(grad_x, grad_gamma, grad_beta) of quantizer(bn(x)) for the gradient ``grad_q`` with respect to the quantizer's value
+    (lsq_bn_ste_backward): g = ``ste_backward(bn_apply(x), grad_q, scales, alpha)`` recomputed in both passes and never stored,
+    grad_beta = sum g, grad_gamma = sum g x^ and grad_x = scale (g - grad_beta / m - x^ grad_gamma / m)."""
+    what = 'lsq_bn_ste_backward'
+    k = 0 if scales is None else int(scales.shape[0])
+    n, c, h, w = _check_bn(what, x, {'scale': scale, 'shift': shift, 'mean': mean, 'invstd': invstd}, {'grad_q': grad_q},
+                           scales, k)
+    bl = bn_train_lib()
+    gx = torch.empty_like(x)
+    gvec = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    ws = _stream_buffer('bn_ste_backward', int(bl.lsq_bn_ste_backward_workspace_bytes(n, c, h, w)), x.device)
+    with _on(x), (_Timed(what, 20 * x.numel(), 0, f'C{c}_H{h}') if _timing is not None else _UNTIMED):
+        check(bl.lsq_bn_ste_backward(x.data_ptr(), grad_q.data_ptr(), n, c, h, w, scale.data_ptr(), shift.data_ptr(),
+                                     mean.data_ptr(), invstd.data_ptr(), k, ptr(scales), float(alpha), gx.data_ptr(),
+                                     gvec[0].data_ptr(), gvec[1].data_ptr(), *_ws_args(ws), stream_ptr(x.device)), what)
+    return gx, gvec[0], gvec[1]
 
 
 def xnor_impl(mode) -> int:

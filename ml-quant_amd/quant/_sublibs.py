@@ -154,6 +154,13 @@ SUBLIBS = (
         'lsq_signw_conv2d_fused_half_plan': (i32, [vp]),
         'lsq_signw_conv2d_fused_half_workspace_bytes': (i64, [vp, i32, i32]),
         'lsq_signw_conv2d_fused_half': (i32, [vp, i32, f32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, sz, vp])}),
+    _entry('bn_train', '|lsq_bn_apply|lsq_quant_values_bn|lsq_bn_ste_backward[a-z0-9_]*', {
+        'lsq_bn_train_workspace_bytes': (sz, [i32, i32, i32, i32]),
+        'lsq_bn_train_stats': (i32, [vp, i32, i32, i32, i32, vp, vp, f32, f32, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        'lsq_bn_apply': (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+        'lsq_quant_values_bn': (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, f32, vp, vp]),
+        'lsq_bn_ste_backward_workspace_bytes': (sz, [i32, i32, i32, i32]),
+        'lsq_bn_ste_backward': (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, f32, vp, vp, vp, vp, sz, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

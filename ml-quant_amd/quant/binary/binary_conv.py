@@ -161,6 +161,14 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: both switches off.  False by default
     fp_half_bn_fold = False
 
+    #: with ``hip_train``: a train-mode ``nn.BatchNorm2d`` in front of this convolution (``XnorBasicBlock``'s bn -> conv pairs,
+    #: fp32 input) is not run in torch but joins the step, ``hip_train._BNQuantConv2dStep``: lsq_bn_train_stats computes the
+    #: batch statistics in one read of x, the quantizer applies fmaf(x, scale, shift) inside its own read and backward is one
+    #: lsq_bn_ste_backward for the straight-through estimator and the batch norm together; bn(x) is never written or saved.
+    #: The statistics and gradients are within the stated roundings of torch's batch norm, not its bits.  A switch of its own;
+    #: False: ``conv(bn(x))`` as before, the default whatever the measurement says in the change that adds it
+    train_bn_fold = False
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
             return self._forward_hip(x)

@@ -44,6 +44,14 @@ backward  grad_x is ONE ``lsq_signw_conv2d_dgrad_half`` (liblsq_hip_conv_train_h
           in lsq_train_wgrad's geometry they are ONE ``lsq_train_wgrad_half`` (liblsq_hip_train_half.so) instead:
           the 16-bit grad_y as it is against the step's own sign planes, grad_b from the same pass -- no ``gy.float()``, no
           ``x.float()``, no ``lsq_quant_values``.
+
+With ``QuantConv2d.train_bn_fold`` (a class attribute, False by default) the train-mode ``nn.BatchNorm2d`` in front of the
+convolution of an ``XnorBasicBlock`` joins the fp32 step: ``_BNQuantConv2dStep`` (liblsq_hip_bn_train.so).
+forward   ``lsq_bn_train_stats`` reads x once (statistics, running buffers, scale / shift); the quantizer, or for fp
+          activations ``lsq_signw_conv2d``, applies fmaf(x, scale, shift) inside its own read -- bn(x) is never written;
+backward  grad_xq as above, then ONE ``lsq_bn_ste_backward``: the straight-through estimator at the recomputed bn(x) and the
+          batch norm's backward (grad_x, grad_gamma, grad_beta) in two reads of x and grad_xq and one write; the MIOpen
+          weight-gradient route reads ``lsq_quant_values_bn``.
 """
 
 from typing import List, Optional
@@ -154,6 +162,36 @@ def _constants(c: int, o: int, device):
     return t
 
 
+def _grad_xq(conv, geom, x, weight, wscales, wbits, gy, _hip):
+    """conv_transpose2d(gy, w_q), the gradient with respect to the quantizer's value, [N, C, H, W] fp32: ONE
+    lsq_signw_conv2d_dgrad over the step's saved weight planes ``wbits`` where the forward kept them (``DGRAD_KERNEL``), else
+    stride-1 sign-weight convolutions of the (zero-inserted) gradient, one per weight plane."""
+    if wbits.numel():
+        return _hip.signw_conv2d_dgrad(gy, wbits, wscales, geom)
+    n, c, h, w = x.shape
+    o = conv.out_channels
+    kh, kw = conv.kernel_size
+    s = conv.stride[0]
+    ph, pw = conv.padding
+    if s == 1:
+        gin = gy
+    else:
+        hu, wu = h + 2 * ph - kh + 1, w + 2 * pw - kw + 1          # rows / columns a stride-1 pass would produce
+        gin = gy.new_zeros((n, o, hu, wu))
+        gin[:, :, ::s, ::s][:, :, :gy.shape[2], :gy.shape[3]] = gy
+    tgeom = _hip.make_geom(n, o, gin.shape[2], gin.shape[3], c, kh, kw, (1, 1), (kh - 1 - ph, kw - 1 - pw), (1, 1), 1)
+    assert _hip.out_hw(tgeom) == (h, w), (_hip.out_hw(tgeom), h, w)
+    ones, zeros = _constants(c, o, x.device)
+    gxq = None
+    for r, u in zip(_weight_residual_planes(weight.detach(), wscales), wscales):
+        wt = r.permute(1, 0, 2, 3).flip(2, 3).contiguous()              # [C, O, KH, KW], taps mirrored
+        tbits, _ = _hip.pack_weight(wt, tgeom, ones)
+        out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+        _hip.signw_conv2d(gin, -1.0, tbits, ones, None, tgeom, out, pre=(u.contiguous(), zeros), res_post=gxq)
+        gxq = out
+    return gxq
+
+
 class _QuantConv2dStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, conv):
@@ -200,36 +238,12 @@ class _QuantConv2dStep(torch.autograd.Function):
         x, weight, wscales, xscales, planes, wbits = ctx.saved_tensors
         xscales = xscales if xscales.numel() else None
         gy = gy.contiguous()
-        n, c, h, w = x.shape
-        o = conv.out_channels
-        kh, kw = conv.kernel_size
-        s = conv.stride[0]
-        ph, pw = conv.padding
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         gx = gw = gb = None
         if need_b:
             gb = gy.sum(dim=(0, 2, 3))
-        if need_x and wbits.numel():
-            gx = _hip.ste_backward(x, _hip.signw_conv2d_dgrad(gy, wbits, wscales, geom), xscales, alpha)
-        elif need_x:
-            # conv_transpose2d(gy, w_q) as stride-1 sign-weight convolutions of the (zero-inserted) gradient
-            if s == 1:
-                gin = gy
-            else:
-                hu, wu = h + 2 * ph - kh + 1, w + 2 * pw - kw + 1          # rows / columns a stride-1 pass would produce
-                gin = gy.new_zeros((n, o, hu, wu))
-                gin[:, :, ::s, ::s][:, :, :gy.shape[2], :gy.shape[3]] = gy
-            tgeom = _hip.make_geom(n, o, gin.shape[2], gin.shape[3], c, kh, kw, (1, 1), (kh - 1 - ph, kw - 1 - pw), (1, 1), 1)
-            assert _hip.out_hw(tgeom) == (h, w), (_hip.out_hw(tgeom), h, w)
-            ones, zeros = _constants(c, o, x.device)
-            gxq = None
-            for r, u in zip(_weight_residual_planes(weight.detach(), wscales), wscales):
-                wt = r.permute(1, 0, 2, 3).flip(2, 3).contiguous()              # [C, O, KH, KW], taps mirrored
-                tbits, _ = _hip.pack_weight(wt, tgeom, ones)
-                out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
-                _hip.signw_conv2d(gin, -1.0, tbits, ones, None, tgeom, out, pre=(u.contiguous(), zeros), res_post=gxq)
-                gxq = out
-            gx = _hip.ste_backward(x, gxq, xscales, alpha)
+        if need_x:
+            gx = _hip.ste_backward(x, _grad_xq(conv, geom, x, weight, wscales, wbits, gy, _hip), xscales, alpha)
         if need_w:
             if planes.numel():
                 gwq = _hip.wgrad(planes, xscales.shape[0], xscales, gy, geom)
@@ -311,6 +325,109 @@ class _QuantConv2dStepHalf(torch.autograd.Function):
                                                           conv.groups)
                     gw = _hip.ste_backward(weight.detach(), gwq, wscales, -1.0)
         return gx, gw, gb, None
+
+
+class _BNQuantConv2dStep(torch.autograd.Function):
+    """``conv(bn(x))`` for a train-mode ``nn.BatchNorm2d`` and fp32 ``x`` (``QuantConv2d.train_bn_fold``): the
+    normalised tensor is never written.  Forward: lsq_bn_train_stats reads x once and gives (scale, shift), which the
+    quantizer (or, for fp activations, the sign-weight convolution) applies inside its own read.  Backward: grad_xq by the
+    routes of ``_QuantConv2dStep``, then ONE lsq_bn_ste_backward for the straight-through estimator and the batch norm
+    together.  Saved: x, the five [C] vectors of the statistics, the weight and the scales -- no tensor of x's shape but x."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, weight, bias, conv, bn):
+        from quant import _hip
+        x = x.contiguous()
+        n, c, h, w = x.shape
+        kh, kw = conv.kernel_size
+        alpha = conv._alpha()
+        geom = _hip.make_geom(n, c, h, w, conv.out_channels, kh, kw, conv.stride, conv.padding, conv.dilation, conv.groups)
+        ho, wo = _hip.out_hw(geom)
+        # the batch norm's train-mode bookkeeping (torch.nn.modules.batchnorm._BatchNorm.forward), then its statistics
+        count = 1
+        running = bn.track_running_stats and bn.running_mean is not None
+        if running and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+            if bn.momentum is None:
+                count = int(bn.num_batches_tracked)
+        stats = _hip.bn_train_stats(x.detach(), None if gamma is None else gamma.detach(), None if beta is None else beta.detach(),
+                                    bn.eps, bn.momentum, bn.running_mean if running else None,
+                                    bn.running_var if running else None, count)
+        mean, var, invstd, scale, shift = stats
+        wscales, wbits, wsum = step_weight_planes(conv, weight.detach(), geom, _hip)
+        y = torch.empty((n, conv.out_channels, ho, wo), dtype=torch.float32, device=x.device)
+        b = None if bias is None else bias.detach()
+        keep_planes = False
+        if conv.x_quant == 'fp':
+            _hip.signw_conv2d(x.detach(), alpha, wbits, wscales, b, geom, y, pre=(scale, shift))
+            xscales = None
+        else:
+            k = conv.x_approximate.n_planes
+            keep_planes = WGRAD_KERNEL and ctx.needs_input_grad[3] and _wgrad_geometry(conv)
+            if keep_planes:
+                planes = zero_planes(geom, k, x.device, _hip)
+            else:
+                planes = step_planes(conv, geom, k, x.device, _hip, (geom.pad_h, geom.pad_w))
+            xscales = step_act_quant(conv, x.detach(), geom, planes, _hip, pre=(scale, shift))
+            _hip.xnor_conv2d(planes, k, xscales, wbits, wsum, wscales, b, geom, y)
+            conv.last_act_scales = xscales
+        ctx.conv, ctx.geom, ctx.alpha = conv, geom, alpha
+        ctx.has_bias, ctx.affine = bias is not None, (gamma is not None, beta is not None)
+        empty = x.new_empty(0, dtype=torch.int64)
+        ctx.save_for_backward(x, mean, var, invstd, scale, shift, weight, wscales,
+                              xscales if xscales is not None else x.new_empty(0), planes if keep_planes else empty,
+                              wbits if (DGRAD_KERNEL and any(ctx.needs_input_grad[:3])) else empty)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        from quant import _hip
+        conv, geom, alpha = ctx.conv, ctx.geom, ctx.alpha
+        x, mean, var, invstd, scale, shift, weight, wscales, xscales, planes, wbits = ctx.saved_tensors
+        xscales = xscales if xscales.numel() else None
+        gy = gy.contiguous()
+        need = ctx.needs_input_grad
+        need_w, need_b = need[3], ctx.has_bias and need[4]
+        gx = ggamma = gbeta = gw = gb = None
+        if need_b:
+            gb = gy.sum(dim=(0, 2, 3))
+        if need[0] or (ctx.affine[0] and need[1]) or (ctx.affine[1] and need[2]):
+            gq = _grad_xq(conv, geom, x, weight, wscales, wbits, gy, _hip)
+            gx, ggamma, gbeta = _hip.bn_ste_backward(x, gq, scale, shift, mean, invstd, xscales, alpha)
+        if need_w:
+            if planes.numel():
+                gwq = _hip.wgrad(planes, xscales.shape[0], xscales, gy, geom)
+            else:
+                xq = _hip.quant_values_bn(x, scale, shift, xscales, alpha)
+                gwq = torch.nn.grad.conv2d_weight(xq, weight.shape, gy, conv.stride, conv.padding, conv.dilation, conv.groups)
+            gw = _hip.ste_backward(weight.detach(), gwq, wscales, -1.0)
+        return (gx if need[0] else None, ggamma if (ctx.affine[0] and need[1]) else None,
+                gbeta if (ctx.affine[1] and need[2]) else None, gw, gb, None, None)
+
+
+def bn_fold_supported(conv, bn, x: torch.Tensor) -> bool:
+    """Whether ``conv(bn(x))`` takes ``train_step_forward_bn``: the class switch ``train_bn_fold`` (and ``hip_train``), both
+    modules training, ``bn`` a plain ``nn.BatchNorm2d`` (not a subclass: SyncBatchNorm's statistics are not one device's), a 4-d
+    fp32 ``x`` that ``supported`` accepts with at least two values per channel (below that torch raises) and at most 65535
+    channels, fp32 batch-norm parameters and buffers.  Anything else keeps ``conv(bn(x))``."""
+    if not (conv.train_bn_fold and conv.hip_train and conv.training and bn.training and type(bn) is torch.nn.BatchNorm2d):
+        return False
+    if not (x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] == bn.num_features and x.shape[1] <= 65535
+            and x.shape[0] * x.shape[2] * x.shape[3] >= 2):
+        return False
+    if any(t is not None and (t.dtype != torch.float32 or t.device != x.device)
+           for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+        return False
+    if torch.is_autocast_enabled('cuda'):
+        return False                      # (under autocast torch decides the batch norm's types)
+    return supported(conv, x)
+
+
+def train_step_forward_bn(conv, bn, x: torch.Tensor) -> torch.Tensor:
+    """``conv(bn(x))`` in train mode through the kernels with the batch norm folded into them (``bn_fold_supported`` holds):
+    differentiable with respect to x, the batch norm's weight and bias and the convolution's; updates ``bn``'s buffers."""
+    return _BNQuantConv2dStep.apply(x, bn.weight, bn.bias, conv.weight, conv.bias, conv, bn)
 
 
 def train_step_forward(conv, x: torch.Tensor) -> torch.Tensor:

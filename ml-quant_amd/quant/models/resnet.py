@@ -261,12 +261,23 @@ class XnorBasicBlock(nn.Module):
                 return self.conv2.fused_forward(first, self.bn2, res_post=first, next_q=nxt, **a2)
             first = self.conv1.fused_forward(x, self.bn1, next_q=(self.bn2, self.conv2), **a1)
             return self.conv2.fused_forward(first, self.bn2, res_pre=sc, next_q=nxt, res_ready=sc_ready, **a2)
-        first = self.nonlin1(self.conv1(self.bn1(x)))
+        first = self.nonlin1(_bn_conv(self.bn1, self.conv1, x))
         if self.double_shortcut:
             first = first + self.shortcut(x)
-            return self.nonlin2(self.conv2(self.bn2(first))) + first
-        second = self.conv2(self.bn2(first)) + self.shortcut(x)
+            return self.nonlin2(_bn_conv(self.bn2, self.conv2, first)) + first
+        second = _bn_conv(self.bn2, self.conv2, first) + self.shortcut(x)
         return self.nonlin2(second)
+
+
+def _bn_conv(bn: nn.Module, conv: QuantConv2d, x: torch.Tensor) -> torch.Tensor:
+    """``conv(bn(x))``.  With ``QuantConv2d.train_bn_fold`` set, a train-mode plain ``nn.BatchNorm2d`` in front of a train step on
+    the kernels (fp32 CUDA input) joins that step, ``hip_train.train_step_forward_bn``: bn(x) is never written.  The switch is
+    read first, so with it off nothing else is looked at."""
+    if conv.train_bn_fold and conv.training:
+        from quant.binary import hip_train
+        if hip_train.bn_fold_supported(conv, bn, x):
+            return hip_train.train_step_forward_bn(conv, bn, x)
+    return conv(bn(x))
 
 
 #: the projection shortcut of an XnorBasicBlock is computed inside the XNOR convolution whose epilogue adds it, for the shapes
