@@ -55,6 +55,13 @@ struct ConvArgs {
   // sum of a multi-launch call lives in `sum`, which the launches before the last write as their fp32 y
   const float* sum;                    // [N][O][Ho][Wo] fp32: the accumulate read of a 16-bit launch (fp32 launches read y)
   int io_dtype;                        // LSQ_DTYPE_F32 (0, every other entry point) | LSQ_DTYPE_BF16 | LSQ_DTYPE_F16: THIS launch's
+  // ---- the NEXT layer's quantizer with GIVEN scales in this layer's epilogue (lsq_xnor_conv2d_chain_fixed; the NQF
+  // instantiations of lsq_xnor_mfma.hip, final pass only): nf_k planes of sign bits, no sum.  The folded batch norm, the
+  // clamp and the consumer's padded layout are nq_scale / nq_shift / nq_alpha (here <= 0: no clamp) / nq_Hp .. nq_pw above.
+  unsigned* nf_planes32;               // or null: plane p at nf_planes32 + p * nf_plane_dwords, [N][O/64][nq_Hp][nq_Wp] as dwords
+  const float* nf_scales;              // [nf_k][N], the layout of lsq_act_quant's `forced`
+  long long nf_plane_dwords;
+  int nf_k;                            // 1..LSQ_MAX_PLANES
 };
 
 // The epilogue's memory accesses in the I/O type T of a kernel instantiation: float (as ever), __bf16 or _Float16.  A 16-bit
@@ -98,6 +105,9 @@ constexpr int kXnorMfmaNotEligible = 1;
 // One launch (one weight plane x kx <= 2 activation planes) on the matrix cores; kXnorMfmaNotEligible when the
 // geometry is not covered (the caller then takes the popcount kernel), else hipGetLastError().
 int xnor_conv_mfma(const ConvArgs& a, int kx, int groups, hipStream_t st);
+// The final launch of lsq_xnor_conv2d_chain_fixed (a.nf_planes32 set, an eligible geometry): the NQF instantiations of the
+// matrix-core kernel, a translation unit of their own (lsq_xnor_chain_fixed.hip); xnor_conv_mfma forwards to it.
+int xnor_conv_mfma_fixed(const ConvArgs& a, int kx, hipStream_t st);
 // Whether xnor_conv_mfma takes the geometry (no launch): what lsq_xnor_conv2d_proj must know before it launches anything.
 bool xnor_conv_mfma_eligible(const ConvArgs& a, int kx, int groups);
 

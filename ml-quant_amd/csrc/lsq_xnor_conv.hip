@@ -22,6 +22,7 @@
 #include "lsq_xnor_conv.h"
 #include "lsq_hip_conv_proj.h"
 #include "lsq_hip_conv_proj_half.h"
+#include "lsq_hip_conv_chain.h"
 
 #include <cstdlib>
 
@@ -275,7 +276,7 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
                             const float* res_post, float* y, void* stream,
                             const int64_t* x_units, float x_alpha, const lsq_next_ls1* next, const lsq_proj* proj = nullptr,
                             bool with_proj = false, int io_dtype = LSQ_DTYPE_F32, void* workspace = nullptr,
-                            size_t workspace_bytes = 0) {
+                            size_t workspace_bytes = 0, const lsq_next_fixed* fixed = nullptr) {
   // io_dtype != LSQ_DTYPE_F32 (lsq_xnor_conv2d_half): y, res_pre and res_post point at 16-bit elements of that type
   if (with_proj && (!proj || !proj->x || !proj->w)) return LSQ_E_NULL;
   if (!xplanes || (!xscales && !x_units) || !wbits || !wsum || !wscales || !y) return LSQ_E_NULL;
@@ -341,6 +342,22 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
       if ((long long)g->N * (g->O / 64) * a.nq_Hp * a.nq_Wp >= (1ll << 30)) return LSQ_E_UNSUPPORTED;
     }
   }
+  if (fixed) {
+    // the next layer's given-scale quantizer in the epilogue (the NQF kernels of lsq_xnor_mfma.hip; pointers and plane counts
+    // were checked by xnor_conv2d_chain_fixed): every refusal here, before any launch; LSQ_E_UNSUPPORTED sends the caller to
+    // lsq_xnor_conv2d + lsq_act_quant
+    if (!xnor_conv_mfma_eligible(a, kx, g->groups) || g->O % 64 || fixed->pad_h < 0 || fixed->pad_w < 0) return LSQ_E_UNSUPPORTED;
+    a.nq_Hp = Ho + 2 * fixed->pad_h; a.nq_Wp = Wo + 2 * fixed->pad_w;
+    a.nq_ph = fixed->pad_h; a.nq_pw = fixed->pad_w;
+    a.nf_plane_dwords = 2ll * g->N * (g->O / 64) * a.nq_Hp * a.nq_Wp;
+    if (a.nf_plane_dwords >= (1ll << 30)) return LSQ_E_UNSUPPORTED;
+    a.nf_planes32 = (unsigned*)fixed->planes;
+    a.nf_scales = fixed->scales;
+    a.nf_k = fixed->k;
+    a.nq_scale = fixed->pre_scale;
+    a.nq_shift = fixed->pre_shift;
+    a.nq_alpha = fixed->clamp_alpha;
+  }
   if (with_proj) {
     // the projection computed in the residual registers (the PROJ kernels of lsq_xnor_mfma.hip): every refusal here, before
     // any launch; LSQ_E_UNSUPPORTED sends the caller to lsq_pointwise_conv + lsq_xnor_conv2d
@@ -390,8 +407,8 @@ static int xnor_conv2d_impl(const uint64_t* xplanes, int kx, const float* xscale
         a.y = a.final_pass ? y : static_cast<float*>(workspace);
         a.sum = static_cast<const float*>(workspace);
       }
-      int e = (impl == 1 && !chained) ? kXnorMfmaNotEligible : xnor_conv_mfma(a, np, g->groups, st);
-      if (e == kXnorMfmaNotEligible && chained) return LSQ_E_UNSUPPORTED;
+      int e = (impl == 1 && !chained && !fixed) ? kXnorMfmaNotEligible : xnor_conv_mfma(a, np, g->groups, st);
+      if (e == kXnorMfmaNotEligible && (chained || fixed)) return LSQ_E_UNSUPPORTED;
       if (e == kXnorMfmaNotEligible) {
         if (a.io_dtype == LSQ_DTYPE_BF16) e = np == 2 ? launch_kx<2, __bf16>(a, g->groups, st) : launch_kx<1, __bf16>(a, g->groups, st);
         else if (a.io_dtype == LSQ_DTYPE_F16) e = np == 2 ? launch_kx<2, _Float16>(a, g->groups, st) : launch_kx<1, _Float16>(a, g->groups, st);
@@ -450,6 +467,19 @@ int xnor_conv2d_proj_half(const uint64_t* xplanes, int kx, const float* xscales,
   return xnor_conv2d_impl(xplanes, kx, xscales, wbits, wsum, kw_planes, wscales, bias, g, act, act_slope,
                           static_cast<const float*>(res_pre), static_cast<const float*>(res_post), static_cast<float*>(y), stream,
                           nullptr, -1.f, nullptr, proj ? &p : nullptr, true, dtype == LSQ_DTYPE_F32 ? -1 : dtype);
+}
+
+// lsq_xnor_conv2d_chain_fixed of liblsq_hip_conv_chain.so (include/lsq_hip_conv_chain.h), which links this library for it.
+// One launch per weight plane (kx <= 2); the quantizer runs in the last one's epilogue.
+int xnor_conv2d_chain_fixed(const uint64_t* xplanes, int kx, const float* xscales, const uint64_t* wbits, const int32_t* wsum,
+                            int kw_planes, const float* wscales, const float* bias, const lsq_conv_geom* g, int act,
+                            const float* act_slope, const float* res_pre, const float* res_post, const lsq_next_fixed* next,
+                            float* y, void* stream) {
+  if (!next || !next->planes || !next->scales) return LSQ_E_NULL;
+  if ((next->pre_scale == nullptr) != (next->pre_shift == nullptr)) return LSQ_E_NULL;
+  if (next->k < 1 || next->k > LSQ_MAX_PLANES || kx < 1 || kx > 2) return LSQ_E_SCHEME;
+  return xnor_conv2d_impl(xplanes, kx, xscales, wbits, wsum, kw_planes, wscales, bias, g, act, act_slope, res_pre, res_post, y,
+                          stream, nullptr, -1.f, nullptr, nullptr, false, LSQ_DTYPE_F32, nullptr, 0, next);
 }
 
 // 0 for a call of one launch (or a geometry the call refuses), else the fp32 running sum: 4 N O Ho Wo

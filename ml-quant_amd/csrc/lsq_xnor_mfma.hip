@@ -72,11 +72,23 @@ extern __shared__ __attribute__((aligned(16))) float s_pw[];         // PROJ: [3
 // a.sum, not from y.  PROJ with a 16-bit T (lsq_xnor_conv2d_proj_half): the projection's x is of type T too -- gathered with
 // 2-byte loads, kept as loaded and widened (exact) in front of the MFMA that multiplies it; proj_w and proj_bias stay fp32 and
 // the projection tile stays in the sixteen fp32 registers rv[], never rounded: y is rounded once, at the store.
-template <int KX, int GG, int TAPS, int NWAVES, int WPC, bool CHAIN, bool FP4, bool PROJ = false, typename T = float>
+//
+// NQF > 0 (FP4, fp32, lsq_xnor_conv2d_chain_fixed): the NEXT layer's quantizer with GIVEN per-sample scales (moving-average
+// inference: no solve, lsq_act_quant's `forced`) on the sixteen values a lane holds once y is stored -- for one or two
+// activation planes on the input side and 1..LSQ_MAX_PLANES on the consumer's.  Per plane p: bit = (t - result) >= 0 with
+// t = clamp(bn(y)) and result the fp32 sum of the +-v_q chosen so far, the result chain of lsq_act_quant's sweeps
+// (chain_eval; for p <= 1 it is the residual itself), one compare, one select and one add per value; the 32 out-channels of the
+// tile are one dword of the consumer's channel word, merged from the two lane halves with v_permlane32_swap and stored by
+// the lower half.  No sum, no atomic, nothing to zero.  t and result live in the registers the accumulators leave; NQF is
+// the number of scales a lane keeps across tiles (2: the 1- and 2-plane schemes, 8: gf-3 .. gf-8), reloaded when the
+// lane's sample changes.
+template <int KX, int GG, int TAPS, int NWAVES, int WPC, bool CHAIN, bool FP4, bool PROJ = false, typename T = float, int NQF = 0>
 __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a) {
   static_assert(!PROJ || (FP4 && !CHAIN), "the projection runs in the unchained fp4 kernel only");
   constexpr bool kF32 = std::is_same<T, float>::value;
   static_assert(kF32 || (FP4 && !CHAIN), "16-bit epilogue I/O: the unchained fp4 kernel only");
+  static_assert(NQF == 0 || (FP4 && kF32 && !(CHAIN || PROJ) && NQF <= LSQ_MAX_PLANES), "given-scale next quantizer: the plain fp32 fp4 kernel only");
+  constexpr bool kNext = CHAIN || NQF > 0;       // a next quantizer of either kind: its folded batch norm, the tile's outputs kept
   constexpr int NT = 64 * NWAVES;
   constexpr int FPS = FP4 ? 1 : 2;               // 16-byte weight fragments per (word, tap) step: int8 K = 32 twice, fp4 K = 64 once
   constexpr int NF = TAPS * GG * FPS;            // 16-byte operand fragments per lane
@@ -88,7 +100,7 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
   // output instead of loops over kernel rows and columns.
   __shared__ __attribute__((aligned(16))) short s_fc[8][8][32];    // |.| <= taps * channels = 4608
   __shared__ __attribute__((aligned(16))) float s_scale[32], s_bias[32], s_slope[32];
-  __shared__ float s_nqs[CHAIN ? 32 : 1], s_nqt[CHAIN ? 32 : 1];      // chained layers: the next quantizer's folded batch norm
+  __shared__ float s_nqs[kNext ? 32 : 1], s_nqt[kNext ? 32 : 1];      // chained layers: the next quantizer's folded batch norm
   __shared__ __attribute__((aligned(16))) float s_pbias[PROJ ? 32 : 1];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int col = lane & 31, hh = lane >> 5;
@@ -226,6 +238,10 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
       c_ns = (a.nq_planes32 && a.nq_scale) ? a.nq_scale[o0 + tid] : 1.f;
       c_nt = (a.nq_planes32 && a.nq_scale) ? a.nq_shift[o0 + tid] : 0.f;
     }
+    if constexpr (NQF > 0) {
+      c_ns = a.nq_scale ? a.nq_scale[o0 + tid] : 1.f;
+      c_nt = a.nq_scale ? a.nq_shift[o0 + tid] : 0.f;
+    }
   }
   // one thread = one (fragment pair, lane) entry: the weight word's dword of the lane's half, eight registers of four
   // bytes +-(64 >> q): bytes (d >> q) & 0x01010101 -> 0x00 / 0xFF masks -> select between the two byte patterns
@@ -271,7 +287,7 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
     s_scale[tid] = c_sc;
     s_bias[tid] = c_bi;
     s_slope[tid] = c_sl;
-    if constexpr (CHAIN) {
+    if constexpr (kNext) {
       s_nqs[tid] = c_ns;
       s_nqt[tid] = c_nt;
     }
@@ -311,6 +327,10 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
     for (int f = 0; f < FPS; ++f) wring[i][f] = s_w[FPS * i + f][lane];
   }
   const int unit_scale = 0x7F7F7F7F;             // E8M0 127 = 2^0 in every byte (fp4: the block scales of both operands)
+  float nfv[NQF > 0 ? NQF : 1];                  // NQF: the consumer's scales of sample nf_n, [plane]
+  int nf_n = -1;
+#pragma unroll
+  for (int p = 0; p < (NQF > 0 ? NQF : 1); ++p) nfv[p] = 0.f;
 #ifdef LSQ_XNOR_CLOCKS
   long long clk[15];
   int nclk = 0;
@@ -515,10 +535,20 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
 
     XCLK();
     // ---- epilogue of this tile: the popcount kernel's arithmetic on the same integers -> the same floats --------
-    float nqv[CHAIN ? 16 : 1];                   // (chained layers: the tile's outputs, kept for the next layer's quantizer)
-    if constexpr (CHAIN) {
+    float nqv[kNext ? 16 : 1];                   // (chained layers: the tile's outputs, kept for the next layer's quantizer)
+    if constexpr (kNext) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) nqv[i] = 0.f;
+    }
+    if constexpr (NQF > 0) {
+      // the consumer's scales of the lane's sample ([k][N], lsq_act_quant's `forced`): requested in front of the epilogue's
+      // arithmetic and stores, used behind them; lanes past the last pixel read sample 0's and store nothing
+      if (fin && ln != nf_n) {
+#pragma unroll
+        for (int p = 0; p < NQF; ++p)
+          if (p < a.nf_k) nfv[p] = a.nf_scales[p * a.N + ln];
+        nf_n = ln;
+      }
     }
     if (cur.n < a.N) {                           // (false only for the lanes past the last pixel)
       // float(acc) = 32 * (b * s) exactly (|.| < 2^18) and xs / 32 is exact, so (xs / 32) * float(acc) is the very
@@ -572,9 +602,48 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
 #endif
 #pragma unroll
       for (int i = 0; i < 16; ++i) epi_store((reinterpret_cast<T*>(a.y) + koff(i)) + yoff, outv[i]);
-      if constexpr (CHAIN) {
+      if constexpr (kNext) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) nqv[i] = outv[i];
+      }
+    }
+    if constexpr (NQF > 0) {
+      if (fin) {                                 // (uniform: the launch of the last weight plane)
+        const bool valid = cur.n < a.N;
+        float tv[16], res[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int cl = ob + (i & 3) + 8 * (i >> 2);                          // channel inside the 32-channel tile
+          float t = nqv[kNext ? i : 0];
+          if (a.nq_scale) t = fmaf(t, s_nqs[kNext ? cl : 0], s_nqt[kNext ? cl : 0]);
+          if (a.nq_alpha > 0.f) t = fminf(fmaxf(t, -a.nq_alpha), a.nq_alpha);
+          tv[i] = t;
+          res[i] = 0.f;
+        }
+        // the lane's dword of the consumer's word: [n][O/64][ho + pad_h][wo + pad_w], half (o0 / 32) & 1 (below 2^30 dwords per plane)
+        const unsigned at = 2u * (unsigned)(((ln * (a.O >> 6) + (o0 >> 6)) * a.nq_Hp + cur.ho + a.nq_ph) * a.nq_Wp + cur.wo + a.nq_pw) +
+                            (unsigned)((o0 >> 5) & 1);
+        unsigned* __restrict__ dst = a.nf_planes32;
+#pragma unroll
+        for (int p = 0; p < NQF; ++p) {
+          if (p < a.nf_k) {                      // (uniform)
+            const float v = nfv[p];
+            unsigned mask = 0u;
+            bool up[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+              up[i] = (tv[i] - res[i]) >= 0.f;                                 // (-0.0 gives 1)
+              mask |= (up[i] ? 1u : 0u) << (ob + (i & 3) + 8 * (i >> 2));
+            }
+            if (p + 1 < NQF && p + 1 < a.nf_k) {                               // (uniform: the last plane needs no new result)
+#pragma unroll
+              for (int i = 0; i < 16; ++i) res[i] = res[i] + (up[i] ? v : -v);
+            }
+            mask |= __builtin_amdgcn_permlane32_swap(mask, mask, false, false)[1];   // lower lanes: | the upper lanes' bits
+            if (valid && hh == 0) dst[at] = mask;
+            dst += a.nf_plane_dwords;
+          }
+        }
       }
     }
     if (CHAIN && fin && a.nq_planes32) {         // (uniform; compiled into the one-plane kernels only)
@@ -643,6 +712,10 @@ __global__ __launch_bounds__(64 * NWAVES, WPC) void xnor_mfma_kernel(ConvArgs a)
 #endif
 }
 
+// Two translation units are made of this file.  lsq_xnor_chain_fixed.hip defines LSQ_XNOR_NQF_TU and includes it: that unit
+// holds the NQF instantiations and their launcher alone, compiled without packed fp32 VALU instructions; this file compiled
+// as itself holds every other instantiation, with the flags (and the code) it had before NQF existed.
+#ifndef LSQ_XNOR_NQF_TU
 template <int KX, int GG, bool FP4 = true, typename T = float>
 int launch(const ConvArgs& a, hipStream_t st) {
   // launch shape per channel count: waves per workgroup, workgroups per CU, and WPC = the waves per SIMD the register
@@ -685,7 +758,52 @@ int launch(const ConvArgs& a, hipStream_t st) {
   }
   return (int)hipGetLastError();
 }
+#else  // LSQ_XNOR_NQF_TU
 
+// lsq_xnor_conv2d_chain_fixed: the final launch of a call, the next layer's given-scale quantizer in its epilogue (NQF = 2 for
+// consumers of one or two planes, LSQ_MAX_PLANES beyond).  The plain fp4 kernel's grid.  Shape = (waves per workgroup, waves
+// per SIMD): the plain kernel's twelve waves, three per SIMD, wherever the compiler fits the quantizer into the 168 registers
+// of that shape without scratch -- every instantiation but two activation planes with eight scales held (36-64 bytes of
+// scratch per lane there), which runs as eight waves, two per SIMD.  Register counts: DESIGN 4.34.
+template <int KX, int GG, int NQF>
+int launch_fixed_nqf(const ConvArgs& a, hipStream_t st) {
+  constexpr bool kTwo = KX == 2 && NQF > 2;
+  constexpr int NWAVES = kTwo ? 8 : 12, WPC = kTwo ? 2 : 3;
+  const long long ntiles = ((long long)a.N * a.Ho * a.Wo + 31) >> 5;
+  const int n_ot = a.O / 32;
+  long long gx = (256 + n_ot - 1) / n_ot;
+  if (gx * NWAVES > ntiles) gx = (ntiles + NWAVES - 1) / NWAVES;
+  hipLaunchKernelGGL((xnor_mfma_kernel<KX, GG, 9, NWAVES, WPC, false, true, false, float, NQF>), dim3((unsigned)gx, (unsigned)n_ot),
+                     dim3(64 * NWAVES), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+template <int KX, int GG>
+int launch_fixed(const ConvArgs& a, hipStream_t st) {
+  return a.nf_k <= 2 ? launch_fixed_nqf<KX, GG, 2>(a, st) : launch_fixed_nqf<KX, GG, LSQ_MAX_PLANES>(a, st);
+}
+
+template <int KX>
+int launch_fixed_gg(const ConvArgs& a, hipStream_t st) {
+  switch (a.cg) {
+    case 64: return launch_fixed<KX, 1>(a, st);
+    case 128: return launch_fixed<KX, 2>(a, st);
+    case 256: return launch_fixed<KX, 4>(a, st);
+    case 512: return launch_fixed<KX, 8>(a, st);
+  }
+  return kXnorMfmaNotEligible;
+}
+
+}  // namespace
+
+int xnor_conv_mfma_fixed(const ConvArgs& a, int kx, hipStream_t st) {
+  return kx == 2 ? launch_fixed_gg<2>(a, st) : launch_fixed_gg<1>(a, st);
+}
+
+}  // namespace lsq
+#endif  // LSQ_XNOR_NQF_TU
+
+#ifndef LSQ_XNOR_NQF_TU
 // lsq_xnor_conv2d_proj: two activation planes, unchained, the projection shortcut in the residual registers (PROJ).  Same
 // grid as launch(): one workgroup per CU, every wave strides over the pixel tiles of its out-channel tile.  The projection
 // weights take dynamic LDS on top of the static tables (more than 64 KB in all at 512 channels: announced once per kernel).
@@ -747,8 +865,9 @@ int launch_gg(const ConvArgs& a, hipStream_t st) {
   }
   if (a.io_dtype == LSQ_DTYPE_BF16) return launch_gg_half<KX, __bf16>(a, st);
   if (a.io_dtype == LSQ_DTYPE_F16) return launch_gg_half<KX, _Float16>(a, st);
+  if (a.nf_planes32 && a.final_pass) return xnor_conv_mfma_fixed(a, KX, st);      // (the NQF kernels: lsq_xnor_chain_fixed.hip)
   // (test hook lsq_debug_xnor_impl(2): rounds 2-5's int8 kernel, the fp4 kernel's comparator -- same bits; plain calls only)
-  if (a.int8_mfma && !a.xunits && !a.nq_planes32) {
+  if (a.int8_mfma && !a.xunits && !a.nq_planes32 && !a.nf_planes32) {
     switch (a.cg) {
       case 64: return launch<KX, 1, false>(a, st);
       case 128: return launch<KX, 2, false>(a, st);
@@ -780,3 +899,4 @@ int xnor_conv_mfma(const ConvArgs& a, int kx, int groups, hipStream_t st) {
 }
 
 }  // namespace lsq
+#endif  // !LSQ_XNOR_NQF_TU

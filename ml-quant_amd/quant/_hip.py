@@ -17,7 +17,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _sublibs
-from ._sublibs import ConvGeom, NextLs1, ConvDgradPlan  # noqa: F401  (the mirrors of the C structs: public names of this module)
+from ._sublibs import ConvGeom, NextLs1, NextFixed, ConvDgradPlan  # noqa: F401  (the mirrors of the C structs: public names of this module)
 
 _LIB_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'lib')
 # (LSQ_HIP_LIB: developer builds, e.g. -DLSQ_PHASE_CLOCKS)
@@ -410,6 +410,33 @@ def xnor_conv2d_chain(planes: torch.Tensor, xscales: Optional[torch.Tensor], x_u
     return True
 
 
+def xnor_conv2d_chain_fixed(planes: torch.Tensor, kx: int, xscales: torch.Tensor, wbits: torch.Tensor, wsum: torch.Tensor,
+                            wscales: torch.Tensor, bias: Optional[torch.Tensor], geom: ConvGeom, y: torch.Tensor, nxt: NextFixed,
+                            relu: bool = False, res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
+                            prelu: Optional[torch.Tensor] = None) -> bool:
+    """lsq_xnor_conv2d with the NEXT layer's quantizer in its epilogue, for a consumer whose scales are given (``nxt``:
+    include/lsq_hip_conv_chain.h): the consumer's ``nxt.k`` planes are what ``act_quant(y, forced=scales)`` would write.
+    Returns False -- nothing launched, nothing written -- where the library refuses the call as unsupported (the caller runs
+    ``xnor_conv2d`` + ``act_quant``: same bits)."""
+    act, slope = _act(relu, prelu, geom.O)
+    m = geom.C * geom.H * geom.W
+    nres = (res_pre is not None) + (res_post is not None)
+    macs = y.numel() * (geom.C // geom.groups) * geom.KH * geom.KW * kx * wscales.shape[0]
+    lib()                                           # (liblsq_hip_conv_chain.so links liblsq_hip.so: the same loaded object)
+    # bytes: the convolution's own plus the consumer's planes written
+    with _on(y), (_Timed('lsq_xnor_conv2d', geom.N * kx * m // 8 + 4 * y.numel() * (1 + nres) + nxt.k * y.numel() // 8, macs,
+                         f'C{geom.C}_H{geom.H}_s{geom.stride_h}', geom.N * kx * m // 8 + 4 * y.numel())
+                  if _timing is not None else _UNTIMED):
+        code = conv_chain_lib().lsq_xnor_conv2d_chain_fixed(planes.data_ptr(), kx, xscales.data_ptr(), wbits.data_ptr(),
+                                                            wsum.data_ptr(), wscales.shape[0], wscales.data_ptr(), ptr(bias),
+                                                            ctypes.byref(geom), act, ptr(slope), ptr(res_pre), ptr(res_post),
+                                                            ctypes.byref(nxt), y.data_ptr(), stream_ptr(y.device))
+    if code == E_UNSUPPORTED:
+        return False
+    check(code, 'lsq_xnor_conv2d_chain_fixed')
+    return True
+
+
 def signw_prepare_weight(wbits: torch.Tensor, planes: int, geom: ConvGeom) -> Optional[torch.Tensor]:
     """The bf16 operand image of lsq_signw_conv2d's 3x3 fast path for the sign planes ``wbits`` (once per eval
     session, next to pack_weight); None when the geometry has no fast path."""
@@ -649,6 +676,7 @@ conv_act_bn_half_lib, conv_act_bn_half_library_path, CONV_ACT_BN_HALF_ABI_VERSIO
 conv_proj_half_lib, conv_proj_half_library_path, CONV_PROJ_HALF_ABI_VERSION = _sublib('conv_proj_half')
 conv_fused_half_lib, conv_fused_half_library_path, CONV_FUSED_HALF_ABI_VERSION = _sublib('conv_fused_half')
 bn_train_lib, bn_train_library_path, BN_TRAIN_ABI_VERSION = _sublib('bn_train')
+conv_chain_lib, conv_chain_library_path, CONV_CHAIN_ABI_VERSION = _sublib('conv_chain')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21

@@ -31,6 +31,15 @@ class NextLs1(ctypes.Structure):
                 ('pad_w', ctypes.c_int32)]
 
 
+class NextFixed(ctypes.Structure):
+    """Mirror of ``lsq_next_fixed``: where lsq_xnor_conv2d_chain_fixed leaves the next layer's planes, quantized with given
+    scales."""
+
+    _fields_ = [('planes', ctypes.c_void_p), ('k', ctypes.c_int32), ('scales', ctypes.c_void_p), ('pre_scale', ctypes.c_void_p),
+                ('pre_shift', ctypes.c_void_p), ('clamp_alpha', ctypes.c_float), ('pad_h', ctypes.c_int32),
+                ('pad_w', ctypes.c_int32)]
+
+
 class ConvDgradPlan(ctypes.Structure):
     """Mirror of ``lsq_conv_dgrad_plan``."""
 
@@ -161,6 +170,9 @@ SUBLIBS = (
         'lsq_quant_values_bn': (i32, [vp, i32, i32, i32, i32, vp, vp, i32, vp, f32, vp, vp]),
         'lsq_bn_ste_backward_workspace_bytes': (sz, [i32, i32, i32, i32]),
         'lsq_bn_ste_backward': (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, f32, vp, vp, vp, vp, sz, vp])}),
+    _entry('conv_chain', '|lsq_xnor_conv2d_chain_fixed', {
+        'lsq_xnor_conv2d_chain_fixed': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, ctypes.POINTER(NextFixed),
+                                              vp, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

@@ -56,6 +56,14 @@ class ActivationQuantizer(nn.Module):
             return self.plane_scales(avg.view(-1, 1).expand(-1, batch))
         return None
 
+    def eval_scales_stamp(self) -> Optional[tuple]:
+        """What ``eval_scales`` reads, by identity: (data_ptr, _version) of the forced scales or of the moving average; None
+        where ``eval_scales`` is None.  Two equal stamps mean the same scales (an in-place write bumps ``_version``)."""
+        src = self._forced_scales
+        if src is None and self.moving_average_mode != MovingAverageMode.off:
+            src = self.moving_avg_module.moving_average
+        return None if src is None else (src.data_ptr(), src._version)
+
     def plane_scales(self, scales: torch.Tensor) -> torch.Tensor:
         return scales.contiguous()
 

@@ -42,6 +42,10 @@ Dispatch of ``forward``:
     with ``fp`` activations hands non-linearity and 16-bit residuals to ONE lsq_signw_conv2d_fused_half
     (liblsq_hip_conv_fused_half.so), which rounds once; with ``fp_half_bn_fold`` on top of it an eval-mode ``pre_bn`` goes
     into that launch's read too instead of running in torch (DESIGN 4.32);
+  * with ``quant.binary.chain.FIXED_SCALES`` set (module switch, False by default): an fp32 eval call with binary activations
+    whose consumer ``next_q`` has GIVEN activation scales (moving-average inference, any binary scheme) leaves that consumer's
+    planes in its own epilogue, lsq_xnor_conv2d_chain_fixed (liblsq_hip_conv_chain.so), and the consumer skips its
+    lsq_act_quant launch -- the same bits (DESIGN 4.34);
   * anything else (CPU tensors, grouped / dilated training convolutions, 16-bit inputs with binary activations without
     ``act_half`` or with ``fp`` activations without ``fp_half``, 16-bit weights, an autocast of another type) -> the torch
     formulation in ``quant.binary``.
@@ -450,6 +454,40 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         keep = (planes, units, pre)
         return nxt, chain.PreQuant(conv, bn, planes, units, (n, self.out_channels, ho, wo), _hip.stream_ptr(device)), keep
 
+    def _fixed_target(self, next_q, n: int, ho: int, wo: int, device, _hip):
+        """``lsq_next_fixed`` for the consumer ``next_q = (bn, conv)`` of this layer's output when that consumer's activation
+        scales are given (``chain.FIXED_SCALES``; moving-average inference, any binary scheme), or None when the pair cannot be
+        chained: (struct, record for the consumer, what must stay alive)."""
+        from quant.binary import chain
+        if next_q is None or not chain.FIXED_SCALES or self.out_channels % 64 or self.x_approximate.n_planes > 2:
+            return None
+        bn, conv = next_q
+        if not isinstance(conv, QuantConv2d) or conv.x_quant == 'fp' or conv.w_quant == 'fp' or conv.training:
+            return None
+        if conv.in_channels != self.out_channels or conv.groups != 1 or isinstance(conv.padding, str) or conv.padding_mode != 'zeros':
+            return None
+        if conv.weight.device != device:
+            return None                 # (a replica whose ``chain_next`` still names the original module, e.g. nn.DataParallel)
+        if bn is not None and (bn.training or not bn.track_running_stats or bn.running_mean is None or bn.running_mean.device != device):
+            return None
+        xq = conv.x_approximate
+        k = xq.n_planes
+        scales = xq.eval_scales(n)
+        if scales is None or k > _hip.MAX_PLANES:
+            return None
+        stamp = xq.eval_scales_stamp()
+        scales = scales.to(device=device, dtype=torch.float32).contiguous()
+        pre = None if bn is None else conv._folded_bn(bn)
+        ph, pw = conv.padding
+        words = n * (self.out_channels // 64) * (ho + 2 * ph) * (wo + 2 * pw)
+        stream = _hip.stream_ptr(device)
+        planes = conv._workspace('prefix', (n, self.out_channels, ho, wo, ph, pw, k, device, stream),
+                                 lambda: torch.zeros((k * words,), dtype=torch.int64, device=device))   # zero halo; the interior is rewritten
+        nxt = _hip.NextFixed(planes.data_ptr(), k, scales.data_ptr(), None if pre is None else pre[0].data_ptr(),
+                             None if pre is None else pre[1].data_ptr(), conv._alpha(), ph, pw)
+        record = chain.PreQuant(conv, bn, planes, None, (n, self.out_channels, ho, wo), stream, scales, stamp)
+        return nxt, record, (planes, scales, pre)
+
     def _proj_in_kernel(self, x: torch.Tensor, chain, sc: ProjectionShortcut) -> bool:
         """Whether this call ends in the plain XNOR launch that can compute the projection shortcut ``sc`` itself: binary
         activations, not a chained 1-bit layer, and an fp32 input with an fp32 ``sc.x`` (lsq_xnor_conv2d_proj) or, with
@@ -537,7 +575,16 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             return y
         xq = self.x_approximate
         k = xq.n_planes
-        if self.x_quant == 'ls-1' and chain.ENABLED:
+        # given scales (chain.FIXED_SCALES): the planes a producer's epilogue cut for THIS call -- this layer, this batch norm,
+        # this stream and shape, and the very scales this call would use (by identity: eval_scales_stamp)
+        fixed_in = None
+        if handed is not None and handed.scales is not None:
+            if (chain.FIXED_SCALES and handed.consumer is self and handed.pre_bn is pre_bn
+                    and handed.stream == _hip.stream_ptr(x.device) and handed.shape == tuple(x.shape)
+                    and handed.stamp is not None and handed.stamp == xq.eval_scales_stamp()):
+                fixed_in = handed
+            handed = None                              # (never the row sums of the ls-1 chain below)
+        if self.x_quant == 'ls-1' and chain.ENABLED and fixed_in is None:
             # chained 1-bit layers: take the planes and row sums the producer's epilogue left for THIS call, and / or leave
             # the consumer's in this call's epilogue
             stream = _hip.stream_ptr(x.device)
@@ -562,8 +609,18 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                     _hip.xnor_conv2d(planes_in, k, scales_in, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu)
                     self.last_act_scales = scales_in
                     return y
-        planes, scales = self._act_planes(x, geom, k, _hip, (geom.pad_h, geom.pad_w, self.groups), pre)
+        if fixed_in is not None:
+            planes, scales = fixed_in.planes, fixed_in.scales
+        else:
+            planes, scales = self._act_planes(x, geom, k, _hip, (geom.pad_h, geom.pad_w, self.groups), pre)
         join()
+        # the consumer's quantizer in this call's epilogue where its scales are given (not beside an in-kernel projection)
+        target = self._fixed_target(next_q, n, ho, wo, x.device, _hip) if chain.FIXED_SCALES and proj is None else None
+        if target is not None and _hip.xnor_conv2d_chain_fixed(planes, k, scales, wbits, wsum, wscales, bias, geom, y, target[0],
+                                                               relu, res_pre, res_post, prelu):
+            self.last_act_scales = scales
+            chain.attach(y, target[1], target[2])
+            return y                                     # (refused: the plain call below, today's route)
         if proj is not None:
             sc, post = proj
             if _hip.xnor_conv2d_proj(planes, k, scales, wbits, wsum, wscales, bias, geom, y, (sc.x, sc.w, sc.b, sc.stride, post),

@@ -7,6 +7,10 @@ to an accumulator, and the next call takes its activation scale from that accumu
 two quantized convolutions, and its read of the activation tensor, disappear.  This module is the host side of the
 hand-over: what a producer attaches to its output tensor (``PreQuant``), and the accumulators of one forward, which are
 zeroed with ONE fill (``scope``).
+
+With GIVEN scales (moving-average inference) every binary scheme's quantizer is an element-wise function of that tensor:
+``lsq_xnor_conv2d_chain_fixed`` (include/lsq_hip_conv_chain.h) writes the consumer's k planes with no sum at all, and the
+record carries the scales instead of row sums (``FIXED_SCALES``).
 """
 
 import contextlib
@@ -29,17 +33,27 @@ MAX_ELEMENTS = 1 << 23
 #: (``lsq_xnor_conv2d_chain`` refuses such a call; at batch 1 or 2 ``MAX_ELEMENTS`` alone would let it through)
 MAX_ROW_ELEMENTS = 1 << 22
 
+#: True: a consumer whose activation scales are GIVEN (moving-average inference, any binary scheme) gets its planes from the
+#: producing convolution's epilogue, ``lsq_xnor_conv2d_chain_fixed`` (include/lsq_hip_conv_chain.h): no ``lsq_act_quant`` launch,
+#: no second read of the tensor.  A switch of its own, independent of ``ENABLED`` (the free-running ls-1 chain, which keeps
+#: precedence where it applies).  False: every route is what it is without the feature -- the default whatever the
+#: measurement says in the change that adds it
+FIXED_SCALES = False
+
 _state = threading.local()
 _arenas = {}
 
 
 class PreQuant:
-    """The next layer's 1-bit input as its producer left it: plane words + row sums in units of 2^e."""
+    """The next layer's binary input as its producer left it: plane words + row sums in units of 2^e (the ls-1 chain), or --
+    ``units`` None -- the ``scales`` [k, N] the ``k`` planes were cut with and ``stamp``, the identity of what the consumer's
+    ``eval_scales`` read when they were (``ActivationQuantizer.eval_scales_stamp``)."""
 
-    __slots__ = ('consumer', 'pre_bn', 'planes', 'units', 'shape', 'stream', 'version')
+    __slots__ = ('consumer', 'pre_bn', 'planes', 'units', 'shape', 'stream', 'version', 'scales', 'stamp')
 
-    def __init__(self, consumer, pre_bn, planes, units, shape, stream):
+    def __init__(self, consumer, pre_bn, planes, units, shape, stream, scales=None, stamp=None):
         self.consumer, self.pre_bn, self.planes, self.units, self.shape, self.stream = consumer, pre_bn, planes, units, shape, stream
+        self.scales, self.stamp = scales, stamp
         self.version = None             # ``_version`` of the tensor the record rides on: an in-place edit of it voids the record
 
 
@@ -90,7 +104,7 @@ def attach(y: torch.Tensor, record: PreQuant, keep) -> None:
 def pending(x: torch.Tensor) -> Optional[PreQuant]:
     """The record a producer left on ``x`` -- unless ``x`` was written to since (a hook, ``x.add_(...)``): the planes and row
     sums describe the values the producer stored, so the consumer must quantize what is there now."""
-    rec = getattr(x, '_lsq_pre', None) if ENABLED else None
+    rec = getattr(x, '_lsq_pre', None) if (ENABLED or FIXED_SCALES) else None
     if rec is not None and rec.version != x._version:
         return None
     return rec
