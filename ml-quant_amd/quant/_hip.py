@@ -677,6 +677,7 @@ conv_proj_half_lib, conv_proj_half_library_path, CONV_PROJ_HALF_ABI_VERSION = _s
 conv_fused_half_lib, conv_fused_half_library_path, CONV_FUSED_HALF_ABI_VERSION = _sublib('conv_fused_half')
 bn_train_lib, bn_train_library_path, BN_TRAIN_ABI_VERSION = _sublib('bn_train')
 conv_chain_lib, conv_chain_library_path, CONV_CHAIN_ABI_VERSION = _sublib('conv_chain')
+weight_train_lib, weight_train_library_path, WEIGHT_TRAIN_ABI_VERSION = _sublib('weight_train')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1699,6 +1700,38 @@ def bn_ste_backward(x: torch.Tensor, grad_q: torch.Tensor, scale: torch.Tensor, 
                                      mean.data_ptr(), invstd.data_ptr(), k, ptr(scales), float(alpha), gx.data_ptr(),
                                      gvec[0].data_ptr(), gvec[1].data_ptr(), *_ws_args(ws), stream_ptr(x.device)), what)
     return gx, gvec[0], gvec[1]
+
+
+# ---- the train-step weight quantizer (include/lsq_hip_weight_train.h)
+WEIGHT_TRAIN_MAX_ROW = 16384      # LSQ_WEIGHT_TRAIN_MAX_ROW: floats of one out-channel row
+
+
+def weight_quant_pack_supported(geom: ConvGeom, scheme: int, k: int, skip: int) -> bool:
+    """Whether ``weight_quant_pack`` takes the weight of ``geom`` (lsq_weight_quant_pack_supported); where not, the caller
+    keeps the torch weight quantizer and ``pack_weight``."""
+    return bool(weight_train_lib().lsq_weight_quant_pack_supported(ctypes.byref(geom), int(scheme), int(k), int(skip)))
+
+
+def weight_quant_pack(w: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip: int):
+    """(wscales [k, O] fp32, wbits int64 [k * words], wsum int32 [k, O, taps]) of the fp32 weight ``w`` [O, C/groups, KH, KW]
+    in one launch (lsq_weight_quant_pack): the scales of the torch weight quantizer's train-mode forward as ``plane_scales()``
+    returns them, and ``pack_weight(w, geom, wscales)``.  ``skip``: the sub-sampling of the ls-2 / ls-T solve."""
+    what = 'lsq_weight_quant_pack'
+
+    def problem():
+        if w.numel() != geom.O * (geom.C // geom.groups) * geom.KH * geom.KW:
+            return f'w of {w.numel()} elements does not match the geometry'
+
+    _check_operands(what, {'w': w}, problem=problem)
+    wl = weight_train_lib()
+    words = lib().lsq_weight_plane_words(ctypes.byref(geom))
+    wscales = torch.empty((k, geom.O), dtype=torch.float32, device=w.device)
+    wbits = torch.empty((k * words,), dtype=torch.int64, device=w.device)
+    wsum = torch.empty((k, geom.O, geom.KH * geom.KW), dtype=torch.int32, device=w.device)
+    with _on(w), (_Timed(what, 4 * w.numel() + 8 * wbits.numel() + 4 * wsum.numel(), 0) if _timing is not None else _UNTIMED):
+        check(wl.lsq_weight_quant_pack(w.data_ptr(), ctypes.byref(geom), int(scheme), int(k), int(skip), wscales.data_ptr(),
+                                       wbits.data_ptr(), wsum.data_ptr(), stream_ptr(w.device)), what)
+    return wscales, wbits, wsum
 
 
 def xnor_impl(mode) -> int:

@@ -9,9 +9,23 @@ from quant.binary.activation_quantization import MovingAverageMode
 from quant.binary.hip_module import zero_planes
 
 
+# With it on, step_weight_planes computes scales, planes and tap sums in one launch (lsq_weight_quant_pack) wherever the
+# library takes the weight; off (the default, as every switch lands), and for refused geometries and weights other than fp32,
+# it is the torch weight quantizer and lsq_pack_weight.
+WEIGHT_KERNEL = False
+_WEIGHT_SKIP = 3        # the sub-sampling WeightQuantizerLS2 / LST.forward defaults to, which the steps call without one
+
+
 def step_weight_planes(mod, weight4: torch.Tensor, geom, _hip):
     """(wscales [planes, O], wbits, wsum) of this step for the detached weight ``weight4`` [O, C, KH, KW]: the scales are
     computed from it and cached in the module's buffers (train mode, weight_quantization.py:29-31), then the planes packed."""
+    wq = mod.w_approximate
+    if WEIGHT_KERNEL and weight4.dtype == torch.float32 and wq.hip_scheme \
+            and _hip.weight_quant_pack_supported(geom, wq.hip_scheme, wq.n_planes, _WEIGHT_SKIP):
+        wscales, wbits, wsum = _hip.weight_quant_pack(weight4.contiguous(), geom, wq.hip_scheme, wq.n_planes, _WEIGHT_SKIP)
+        with torch.no_grad():
+            wq._store(wscales)            # (v1..vk; ls-T has the one buffer: zip stops there)
+        return wscales, wbits, wsum
     with torch.no_grad():
         mod.w_approximate(weight4)
         wscales = mod.w_approximate.plane_scales().to(torch.float32).contiguous()

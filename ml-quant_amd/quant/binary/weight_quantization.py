@@ -18,6 +18,8 @@ class _CachedScaleQuantizer(nn.Module):
 
     n_scales = 1
     scheme = ''
+    hip_scheme = 0      # LSQ_SCHEME_* of include/lsq_hip.h
+    n_planes = 1        # sign planes of the scheme: rows of plane_scales()
 
     def __init__(self, size: int) -> None:
         super().__init__()
@@ -40,6 +42,7 @@ class WeightQuantizerLS1(_CachedScaleQuantizer):
     """Least squares, 1 bit."""
 
     scheme = 'ls-1'
+    hip_scheme = 1
 
     def forward(self, w: torch.Tensor) -> torch.Tensor:
         if self.training:
@@ -55,6 +58,8 @@ class WeightQuantizerLS2(_CachedScaleQuantizer):
 
     n_scales = 2
     scheme = 'ls-2'
+    hip_scheme = 2
+    n_planes = 2
 
     def forward(self, w: torch.Tensor, skip: int = 3) -> torch.Tensor:
         if self.training:
@@ -69,6 +74,8 @@ class WeightQuantizerLST(_CachedScaleQuantizer):
     """Least squares, ternary."""
 
     scheme = 'ls-T'
+    hip_scheme = 3
+    n_planes = 2
 
     def forward(self, w: torch.Tensor, skip: int = 3) -> torch.Tensor:
         if self.training:
@@ -89,6 +96,8 @@ class WeightQuantizerGF(_CachedScaleQuantizer):
         self.n_scales = k
         self.k = k
         self.scheme = f'gf-{k}'
+        self.hip_scheme = 4
+        self.n_planes = k
         super().__init__(size)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
