@@ -20,7 +20,8 @@ struct FusedArgs {
   int N;
   int ternary;
   int debug;                // developer / test switches: 1 every flagged bin through the block path, 2 a 2048-key list,
-                            // 4 no windowed level-1 histogram (the round-2..4 solve only), 8 windowed histogram built, then dropped
+                            // 4 no windowed level-1 histogram (the round-2..4 solve only), 8 windowed histogram built, then dropped,
+                            // 16 no row-resident form (the two-read kernel for every shape)
   unsigned win_k0;          // windowed level-1 histogram (set by fused_act_quant): fine bin of key k >= win_k0 is
   int win_sh;               // (k - win_k0) >> win_sh, 8192 bins up to the top of the clamp value's binade; 0: off
   const float* forced;      // [2][N] scales given by the caller (moving-average inference): no solve, planes only
@@ -36,5 +37,10 @@ constexpr int kFusedNotEligible = 1;   // the shape is left to the streaming thr
 
 // LSQ_OK, an hipError_t, or kFusedNotEligible (nothing launched).  skip is the reference's 3.
 int fused_act_quant(const FusedArgs& a, hipStream_t st);
+
+// The row-resident form of the windowed ls-2 / ls-T kernel (lsq_act_resident.hip): one read of a row whose pass-2 items are at
+// most one per lane.  Called by fused_act_quant for the shapes of its table, with the pass-2 width and the key triples per
+// lane of its own launch (the fall-back of single rows); kFusedNotEligible when no instantiation takes the shape.
+int resident_act_quant(const FusedArgs& a, int vecf, long long need, hipStream_t st);
 
 }  // namespace lsq

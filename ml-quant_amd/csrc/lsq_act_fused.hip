@@ -1295,6 +1295,27 @@ static __device__ __forceinline__ bool win_plan(FusedLds* lds, unsigned n, unsig
   return true;
 }
 
+// S5: one wave per flagged fine bin, and the run of the row's largest key (shared by win_sweep and the row-resident sweep).
+static __device__ __forceinline__ void win_resolve(FusedLds* lds, unsigned n, unsigned ns, unsigned maxkey, bool ternary, Best& best) {
+  const int tid = threadIdx.x, wid = tid >> 6;
+  WinLds& w = lds->a.w;
+  for (unsigned s = (unsigned)wid; s < ns; s += kWaves) resolve_wslot(lds, n, s, ternary, best);
+  if (tid == kThreads - 1 && w.run.pad) {                      // (the last wave has the fewest slots)
+    const WSlot sl = w.run;
+    const double v = (double)key_value(maxkey);
+    bool hit;
+    [[clang::always_inline]] hit = run_has_candidate(v, sl.cnt, sl.r0, sl.p0, INFINITY, n, lds->total, ternary);   // (a call here
+    // would save the early request's registers to scratch around it)
+    if (hit) {
+      Best cb;
+      cb.cost = cost_of(v, sl.r0, sl.p0, sl.cnt, n, lds->total, ternary);
+      cb.order = sl.r0;
+      cb.value = key_value(maxkey);
+      if (better(cb, best)) best = cb;
+    }
+  }
+}
+
 // Part 2 (S4-S5): the keys of the flagged fine bins out of the registers, one wave per bin.  Only run when win_plan said
 // yes: the early request of pass 2 (keys_dead) is DEFINED here and nowhere else -- a join of this path with the fall-back's
 // (which still holds all the keys) would have both register sets live at once, and the allocator then homes the request in
@@ -1302,7 +1323,6 @@ static __device__ __forceinline__ bool win_plan(FusedLds* lds, unsigned n, unsig
 template <int NK, class Early>
 static __device__ __forceinline__ void win_sweep(FusedLds* lds, unsigned n, unsigned maxkey, bool ternary,
                                                  const unsigned (&kreg)[NK], Early keys_dead, Best& best) {
-  const int tid = threadIdx.x, wid = tid >> 6;
   const unsigned k0 = lds->args.win_k0;
   const int sh = lds->args.win_sh;
   WinLds& w = lds->a.w;
@@ -1344,22 +1364,7 @@ static __device__ __forceinline__ void win_sweep(FusedLds* lds, unsigned n, unsi
   FMARK(5);
   FMARK(6);
   FMARK(7);
-  // ---- S5: one wave per flagged fine bin
-  for (unsigned s = (unsigned)wid; s < ns; s += kWaves) resolve_wslot(lds, n, s, ternary, best);
-  if (tid == kThreads - 1 && w.run.pad) {                      // (the last wave has the fewest slots)
-    const WSlot sl = w.run;
-    const double v = (double)key_value(maxkey);
-    bool hit;
-    [[clang::always_inline]] hit = run_has_candidate(v, sl.cnt, sl.r0, sl.p0, INFINITY, n, lds->total, ternary);   // (a call here
-    // would save the early request's registers to scratch around it)
-    if (hit) {
-      Best cb;
-      cb.cost = cost_of(v, sl.r0, sl.p0, sl.cnt, n, lds->total, ternary);
-      cb.order = sl.r0;
-      cb.value = key_value(maxkey);
-      if (better(cb, best)) best = cb;
-    }
-  }
+  win_resolve(lds, n, ns, maxkey, ternary, best);
   FMARK(8);
 #ifdef LSQ_PHASE_CLOCKS
   if (threadIdx.x == 0 && blockIdx.x < 1024) {
@@ -1959,6 +1964,189 @@ static __device__ __attribute__((noinline)) void run_round2(FusedLds* lds) {
   lds_barrier();                                 // every wave has left the windowed tables (and read the arguments)
   run<U, VEC, false>(a, lds);
 }
+
+#if defined(LSQ_RESIDENT_TU)
+// ---------------------------------------------------------------------------------------------
+// Row-resident form (rows whose pass-2 items are at most one per lane: 7 x 7 x 512, 14 x 14 x 256): the row is read ONCE,
+// in pass 2's mapping -- lane = VEC pixels x 64 channels --, and its clamped values stay in registers (64 * VEC per lane)
+// from the load to the last plane word.  Of the channels 3q, 3q + 1, 3q + 2 of a pixel exactly one is a sub-sampled
+// element (flat index (c0 + cc) HW + p + v divisible by 3; HW % 3 != 0, so the residue steps by +-1 per channel): WHICH
+// one is a property of the lane and the pixel, so histogram and sweep pick it with two selects and every lane runs
+// 22 keys per pixel through them (channel 63 is a sub-sampled element only for the lanes whose pattern starts at 0).
+// The windowed plan, the ranking and the argmin are win_plan / win_resolve / finish_best unchanged; the histogram holds the
+// same integer counts and sums in any order, so scales and planes are those of run<U, VECF, true> bit for bit.  A row the
+// windowed tables cannot take is handed to the round-2 solve from its first load on (run_round2, as run does).
+template <int U, int VEC, int VECF>
+static __device__ __forceinline__ void run_resident(const FusedArgs& a, FusedLds* lds) {
+  constexpr int NQ = 22;                         // keys per pixel: the triples 3q .. 3q + 2 (q < 21) and channel 63
+  const int row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const float* __restrict__ xrow = a.x + (long long)row * a.row_elems;
+  for (int i = tid; i < L1_BINS; i += kThreads) lds->a.hist1[i] = 0ull;
+  const unsigned win_k0 = a.win_k0;
+  const int win_sh = a.win_sh;
+  const unsigned low_base = (unsigned)(lds->a.w.hist_low - lds->a.hist1);
+  for (int i = tid; i < kLowBins; i += kThreads) lds->a.w.hist_low[i] = 0ull;
+  for (int i = tid; i < (L1_BINS + 2) / 2; i += kThreads) reinterpret_cast<unsigned*>(lds->a.w.role)[i] = 0u;
+  if (tid == 0) lds->a.w.n_groups = lds->a.w.n_slots = lds->a.w.flags = lds->a.w.run.pad = 0u;
+  if (tid == 0) lds->args = a;
+  const bool affine = a.pre_scale != nullptr;
+  if (affine) {
+    for (int i = tid; i < a.C; i += kThreads) {
+      lds->bn_s[i] = a.pre_scale[i];
+      lds->bn_t[i] = a.pre_shift[i];
+    }
+  }
+  lds_barrier();
+
+  // the lane's item, as pass2_full numbers them (the host launches this form only when items <= kThreads and VEC | HW)
+  const int HW = a.H * a.W;
+  const int PV = HW / VEC;
+  const bool have = tid < a.Gt * PV;
+  const int item = have ? tid : 0;
+  const int j = item / PV;
+  const int p = (item - j * PV) * VEC;
+  const int grp = j / a.Gg;
+  const int c0 = grp * a.cg + (j - grp * a.Gg) * 64;
+  const long long M = a.row_elems;
+  const unsigned n = (unsigned)((M + 2) / 3);
+  const bool ternary = a.ternary != 0;
+  float val[64][VEC];
+  // which channel of a triple is the sub-sampled one: cc * (HW % 3) + (c0 HW + p + v) == 0 (mod 3)
+  bool sel0[VEC], sel1[VEC];
+  {
+    const unsigned m = (unsigned)(((long long)c0 * HW + p) % 3);
+    const bool up = HW % 3 == 1;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const unsigned t = (m + (unsigned)v) % 3u;
+      const unsigned k = up ? (3u - t) % 3u : t;
+      sel0[v] = k == 0u;
+      sel1[v] = k == 1u;
+    }
+  }
+  auto sub_value = [&](int q, int v) {           // (q and v are compile-time after unrolling)
+    return q < NQ - 1 ? (sel0[v] ? val[3 * q][v] : (sel1[v] ? val[(3 * q + 1) & 63][v] : val[(3 * q + 2) & 63][v])) : val[63][v];
+  };
+  unsigned mk = kNoKey, xk = 0u;
+  if (have) {
+    const float* __restrict__ q = xrow + (long long)c0 * HW + p;
+#pragma unroll
+    for (int cc = 0; cc < 64; ++cc, q += HW) {
+      if constexpr (VEC == 2) {
+        const float2 t = *reinterpret_cast<const float2*>(q);
+        val[cc][0] = t.x; val[cc][1 % VEC] = t.y;
+      } else {
+        val[cc][0] = *q;
+      }
+    }
+    if (affine) {
+      const float* __restrict__ bs = lds->bn_s + c0;
+      const float* __restrict__ bt = lds->bn_t + c0;
+#pragma unroll
+      for (int cc = 0; cc < 64; ++cc) {
+        const float sc = bs[cc], sh = bt[cc];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) val[cc][v] = fmaf(val[cc][v], sc, sh);
+      }
+    }
+#pragma unroll
+    for (int cc = 0; cc < 64; ++cc)
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) val[cc][v] = clamp_sym(val[cc][v], a.alpha);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+#pragma unroll
+      for (int q3 = 0; q3 < NQ; ++q3) {
+        const unsigned key = abs_key(sub_value(q3, v));
+        if (q3 < NQ - 1 || sel0[v]) {
+          hist_add_win(lds, key, win_k0, win_sh, low_base);
+          mk = min(mk, key);
+          xk = max(xk, key);
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int cc = 0; cc < 64; ++cc)
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) val[cc][v] = 0.f;
+  }
+  unsigned minkey = mk, maxkey = xk;
+  block_minmax(minkey, maxkey, lds);               // (its barriers also close the histogram)
+  if (tid == 0) lds->maxkey = maxkey;
+  // (readfirstlane and if / else as in run: the compiler must see that the whole workgroup takes one side, and that nothing
+  //  of the resident side is live across the call)
+  if (__builtin_amdgcn_readfirstlane((int)win_plan(lds, n, minkey, maxkey, ternary)) == 0) {
+    run_round2<U, VECF>(lds);                      // (the resident values are dead here: the row is read again)
+  } else {
+    Best best;
+    best.cost = INFINITY;
+    best.order = kNoKey;
+    best.value = 0.f;
+    WinLds& w = lds->a.w;
+    const unsigned ns = (unsigned)__builtin_amdgcn_readfirstlane((int)w.n_slots);
+    // S4 from the resident values: table look-ups in groups of 11 independent loads, the rare hits captured into their
+    // bin's arena / folded into the successor minimum (win_sweep's S4, the key one v_and away from its value)
+    if (have) {
+      constexpr int G = NQ / 2;
+  #pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+  #pragma unroll
+        for (int g0 = 0; g0 < NQ; g0 += G) {
+          unsigned key[G], ent[G];
+  #pragma unroll
+          for (int g = 0; g < G; ++g) {
+            key[g] = abs_key(sub_value(g0 + g, v));
+            if (g0 + g == NQ - 1) key[g] = sel0[v] ? key[g] : kNoKey;
+            ent[g] = w.role[min((key[g] - win_k0) >> win_sh, (unsigned)L1_BINS)];   // (below the window / no key: wraps past the table)
+          }
+  #pragma unroll
+          for (int g = 0; g < G; ++g) {
+            if (ent[g] != 0u) {
+              const unsigned own = ent[g] & 0xFFu, below = ent[g] >> 8;
+              if (own) {
+                const unsigned pos = atomicAdd(&w.fill[own - 1u], 1u);
+                w.arena[own - 1u][pos & (unsigned)(kWinTask - 1)] = key[g];
+              }
+              if (below && key[g] < w.succ[below - 1u]) atomicMin(&w.succ[below - 1u], key[g]);
+            }
+          }
+        }
+      }
+    }
+    lds_barrier();
+    win_resolve(lds, n, ns, maxkey, ternary, best);
+    const float v1 = finish_best(lds, n, minkey, ternary, best);
+    // pass 2 from the registers: pass2_full's arithmetic (|clamped x| = min(|x|, alpha) and the sign is the input's)
+    double acc = 0.0;
+    if (have) {
+      unsigned long long* __restrict__ prow0 = a.planes + (long long)row * a.row_words;
+      unsigned long long* __restrict__ prow1 = prow0 + a.plane_words;
+  #pragma unroll
+      for (int v = 0; v < VEC; ++v) {
+        unsigned w0[2] = {0u, 0u}, w1[2] = {0u, 0u};
+        float facc = 0.f;
+  #pragma unroll
+        for (int cc = 0; cc < 64; ++cc) push_bits(w0[cc >> 5], w1[cc >> 5], facc, val[cc][v], fabsf(val[cc][v]) - v1);
+        acc += (double)facc;
+        const int pix = p + v;
+        const int h = pix / a.W;
+        const int wc = pix - h * a.W;
+        const long long widx = ((long long)j * a.Hp + h + a.pad_h) * a.Wp + wc + a.pad_w;
+        prow0[widx] = (unsigned long long)__brev(w0[0]) | ((unsigned long long)__brev(w0[1]) << 32);
+        prow1[widx] = (unsigned long long)__brev(w1[0]) | ((unsigned long long)__brev(w1[1]) << 32);
+      }
+    }
+    const double tot = block_sum(acc, lds);
+    if (tid == 0) {
+      a.scales[row] = v1;
+      a.scales[(long long)a.N + row] = ternary ? v1 : (float)(tot / (double)M);
+      if (a.trace) a.trace[row] = (int)lds->best_order;
+    }
+  }
+}
+#endif
 };  // struct Impl
 
 // WIN: windowed level-1 histogram (solve_windowed) with the round-2 solve as the fall-back of single rows; !WIN: the
@@ -2134,7 +2322,43 @@ int launch(const FusedArgs& a, int vec, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
+#if defined(LSQ_RESIDENT_TU)
+// U, VECF: the instantiation run<U, VECF, true> the two-read form takes for the same shape (the fall-back of single rows)
+template <int T, int U, int VEC, int VECF>
+__global__ __launch_bounds__(T) void aq_resident_kernel(FusedArgs a) {
+  using I = Impl<T>;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[sizeof(typename I::FusedLds)];
+  I::template run_resident<U, VEC, VECF>(a, reinterpret_cast<typename I::FusedLds*>(smem));
+}
+#endif
+
 }  // namespace
+
+#if defined(LSQ_RESIDENT_TU)
+// The row-resident instantiations (csrc/lsq_act_resident.hip compiles this file a second time for them alone).  `vecf` and
+// `need` are what fused_act_quant worked out for its own launch of the same shape.
+int resident_act_quant(const FusedArgs& a, int vecf, long long need, hipStream_t st) {
+  constexpr int T = 512;
+  const long long HW = (long long)a.H * a.W;
+  const int vec = HW % 2 == 0 ? 2 : 1;
+  if (!a.win_sh || a.forced || a.greedy || HW % 3 == 0 || (a.cg & 63) != 0 || a.C > kBnCap || (long long)a.Gt * (HW / vec) > T)
+    return kFusedNotEligible;
+  if (vec == 1 && vecf == 1 && need <= 5) hipLaunchKernelGGL((aq_resident_kernel<T, 5, 1, 1>), dim3(a.N), dim3(T), 0, st, a);
+  else if (vec == 2 && vecf == 4 && need > 5 && need <= 9) hipLaunchKernelGGL((aq_resident_kernel<T, 9, 2, 4>), dim3(a.N), dim3(T), 0, st, a);
+  else return kFusedNotEligible;
+  return (int)hipGetLastError();
+}
+#else
+
+// Shapes (C, H, W; one group) that take the row-resident form: those whose launches measured faster with it in the kernel
+// trace; every other shape keeps the two-read kernels.  tests/golden/resident_shapes.py restates the table.
+static bool resident_shape(const FusedArgs& a) {
+  static constexpr int kResidentShapes[][3] = {{512, 7, 7}, {256, 14, 14}};
+  if (a.cg != a.C) return false;
+  for (const auto& s : kResidentShapes)
+    if (a.C == s[0] && a.H == s[1] && a.W == s[2]) return true;
+  return false;
+}
 
 int fused_act_quant(const FusedArgs& a_in, hipStream_t st) {
   FusedArgs a = a_in;
@@ -2177,6 +2401,11 @@ int fused_act_quant(const FusedArgs& a_in, hipStream_t st) {
   if (a.greedy) return launch_greedy<T>(a, vec, st);
   const long long ntrip = (M / 4 + 2) / 3;
   const long long need = (ntrip + T - 1) / T;        // triples (4 keys each) per lane
+  // rows that fit the register file in pass 2's mapping: one read (debug 16: the two-read kernel, the comparator of the tests)
+  if (a.win_sh && !(a.debug & 16) && resident_shape(a)) {
+    const int e = resident_act_quant(a, vec, need, st);
+    if (e != kFusedNotEligible) return e;
+  }
 #ifdef LSQ_DEV_U
   return need <= LSQ_DEV_U ? launch<T, LSQ_DEV_U>(a, vec, st) : kFusedNotEligible;
 #else
@@ -2196,5 +2425,6 @@ extern "C" int lsq_debug_read_win_stats(int* host4096) {
   return (int)hipMemcpyFromSymbol(host4096, HIP_SYMBOL(g_win_stats), 4096 * sizeof(int));
 }
 #endif
+#endif  // !LSQ_RESIDENT_TU
 
 }  // namespace lsq
