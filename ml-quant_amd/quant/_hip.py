@@ -678,6 +678,7 @@ conv_fused_half_lib, conv_fused_half_library_path, CONV_FUSED_HALF_ABI_VERSION =
 bn_train_lib, bn_train_library_path, BN_TRAIN_ABI_VERSION = _sublib('bn_train')
 conv_chain_lib, conv_chain_library_path, CONV_CHAIN_ABI_VERSION = _sublib('conv_chain')
 weight_train_lib, weight_train_library_path, WEIGHT_TRAIN_ABI_VERSION = _sublib('weight_train')
+conv_xnor_gen_lib, conv_xnor_gen_library_path, CONV_XNOR_GEN_ABI_VERSION = _sublib('conv_xnor_gen')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1732,6 +1733,63 @@ def weight_quant_pack(w: torch.Tensor, geom: ConvGeom, scheme: int, k: int, skip
         check(wl.lsq_weight_quant_pack(w.data_ptr(), ctypes.byref(geom), int(scheme), int(k), int(skip), wscales.data_ptr(),
                                        wbits.data_ptr(), wsum.data_ptr(), stream_ptr(w.device)), what)
     return wscales, wbits, wsum
+
+
+# ---- the general fp4 matrix-core XNOR convolution (include/lsq_hip_conv_xnor_gen.h)
+def xnor_conv2d_gen_supported(geom: ConvGeom, kx: int, kw_planes: int) -> bool:
+    """Whether ``xnor_conv2d_gen`` takes the geometry with ``kx`` activation and ``kw_planes`` weight planes
+    (lsq_xnor_conv2d_gen_supported, host only); where not, the caller keeps ``xnor_conv2d``."""
+    return bool(conv_xnor_gen_lib().lsq_xnor_conv2d_gen_supported(ctypes.byref(geom), int(kx), int(kw_planes)))
+
+
+def xnor_mfma_eligible(geom: ConvGeom, kx: int, outputs: int) -> bool:
+    """The geometries lsq_xnor_conv2d already runs on its tuned fp4 matrix-core kernel (xnor_conv_mfma_eligible of
+    csrc/lsq_xnor_mfma.hip): ``xnor_conv2d_gen`` is not for them."""
+    return (geom.KH, geom.KW, geom.groups, geom.dil_w) == (3, 3, 1, 1) and geom.C in (64, 128, 256, 512) and geom.O % 32 == 0 \
+        and kx in (1, 2) and outputs < XNOR_MFMA_MAX_OUTPUTS and act_plane_words(geom) * kx < (1 << 30)
+
+
+def xnor_conv2d_gen(planes: torch.Tensor, kx: int, xscales: torch.Tensor, wbits: torch.Tensor, wsum: torch.Tensor,
+                    wscales: torch.Tensor, bias: Optional[torch.Tensor], geom: ConvGeom, y: torch.Tensor,
+                    relu: bool = False, res_pre: Optional[torch.Tensor] = None,
+                    res_post: Optional[torch.Tensor] = None, prelu: Optional[torch.Tensor] = None) -> bool:
+    """``xnor_conv2d`` on the general fp4 matrix-core kernel (lsq_xnor_conv2d_gen): 1x1, 5x5, 7x7 and asymmetric kernels,
+    dilation, any multiple of 64 input channels; the same operands, the same bits.  Returns False -- nothing launched, nothing
+    written -- where the library refuses the call as unsupported (the caller runs ``xnor_conv2d``)."""
+    what = 'lsq_xnor_conv2d_gen'
+    ho, wo = out_hw(geom)
+    taps = geom.KH * geom.KW
+
+    def problem():
+        if tuple(y.shape) != (geom.N, geom.O, ho, wo):
+            return f'y of shape {tuple(y.shape)} does not match the geometry'
+        if planes.numel() < kx * act_plane_words(geom) or xscales.numel() < kx * geom.N:
+            return f'{kx} activation planes need {kx * act_plane_words(geom)} words and {kx * geom.N} scales'
+        if wscales.dim() != 2 or wscales.shape[1] != geom.O or wsum.numel() != wscales.shape[0] * geom.O * taps:
+            return 'wscales must be [planes, O] and wsum [planes, O, taps]'
+        if wbits.numel() < wscales.shape[0] * lib().lsq_weight_plane_words(ctypes.byref(geom)):
+            return 'wbits is shorter than the weight planes of the geometry'
+        for name, t in (('bias', bias), ('res_pre', res_pre), ('res_post', res_post)):
+            if t is not None and t.numel() != (geom.O if name == 'bias' else y.numel()):
+                return f'{name} has {t.numel()} elements'
+
+    fp32 = {'xscales': xscales, 'wscales': wscales, 'y': y}
+    fp32.update({k: v for k, v in (('bias', bias), ('res_pre', res_pre), ('res_post', res_post)) if v is not None})
+    _check_operands(what, fp32, int64={'planes': planes, 'wbits': wbits}, int32={'wsum': wsum}, problem=problem)
+    act, slope = _act(relu, prelu, geom.O)
+    m = geom.C * geom.H * geom.W
+    macs = y.numel() * geom.C * taps * kx * wscales.shape[0]
+    nres = (res_pre is not None) + (res_post is not None)
+    gl = conv_xnor_gen_lib()
+    with _on(y), (_Timed(what, geom.N * kx * m // 8 + 4 * y.numel() * (1 + nres), macs, f'C{geom.C}_H{geom.H}_s{geom.stride_h}',
+                         geom.N * kx * m // 8 + 4 * y.numel()) if _timing is not None else _UNTIMED):
+        code = gl.lsq_xnor_conv2d_gen(planes.data_ptr(), kx, xscales.data_ptr(), wbits.data_ptr(), wsum.data_ptr(),
+                                      wscales.shape[0], wscales.data_ptr(), ptr(bias), ctypes.byref(geom), act, ptr(slope),
+                                      ptr(res_pre), ptr(res_post), y.data_ptr(), stream_ptr(y.device))
+    if code == E_UNSUPPORTED:
+        return False
+    check(code, what)
+    return True
 
 
 def xnor_impl(mode) -> int:

@@ -176,6 +176,9 @@ SUBLIBS = (
     _entry('weight_train', '|lsq_weight_quant_pack[a-z0-9_]*', {
         'lsq_weight_quant_pack_supported': (i32, [gp, i32, i32, i32]),
         'lsq_weight_quant_pack': (i32, [vp, gp, i32, i32, i32, vp, vp, vp, vp])}),
+    _entry('conv_xnor_gen', '|lsq_xnor_conv2d_gen[a-z0-9_]*', {
+        'lsq_xnor_conv2d_gen_supported': (i32, [gp, i32, i32]),
+        'lsq_xnor_conv2d_gen': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, vp, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

@@ -173,6 +173,14 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: False: ``conv(bn(x))`` as before, the default whatever the measurement says in the change that adds it
     train_bn_fold = False
 
+    #: the plain eval call of the binary-activation branch takes lsq_xnor_conv2d_gen, the general fp4 matrix-core kernel, for
+    #: the geometries lsq_xnor_conv2d serves on its popcount kernel -- 1x1, 5x5, 7x7 and asymmetric kernels, dilation, input
+    #: channels such as 192, 320 or 1024 -- wherever lsq_xnor_conv2d_gen_supported says yes: the same operands, the same bits.
+    #: The 3x3 layers of the tuned matrix-core kernel and the chained, fixed-scale, projection and 16-bit routes are not
+    #: touched.  A switch of its own; False: lsq_xnor_conv2d, the default whatever the measurement says in the change that adds
+    #: it
+    xnor_general = False
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
             return self._forward_hip(x)
@@ -606,7 +614,8 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                         chain.attach(y, target[1], target[2])
                     return y
                 if handed is None and scales_in is not None:   # outside the matrix-core kernel: the plain call, same planes
-                    _hip.xnor_conv2d(planes_in, k, scales_in, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu)
+                    self._xnor_plain(_hip, planes_in, k, scales_in, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post,
+                                     prelu)
                     self.last_act_scales = scales_in
                     return y
         if fixed_in is not None:
@@ -631,6 +640,15 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                 res_post = sc.tensor()
             else:
                 res_pre = sc.tensor()
-        _hip.xnor_conv2d(planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu)
+        self._xnor_plain(_hip, planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu)
         self.last_act_scales = scales
         return y
+
+    def _xnor_plain(self, _hip, planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu):
+        """The plain eval call: lsq_xnor_conv2d, or with ``xnor_general`` lsq_xnor_conv2d_gen first for the geometries the
+        popcount kernel would serve (refused: lsq_xnor_conv2d, same bits)."""
+        if self.xnor_general and not _hip.xnor_mfma_eligible(geom, k, y.numel()) \
+                and _hip.xnor_conv2d_gen_supported(geom, k, wscales.shape[0]) \
+                and _hip.xnor_conv2d_gen(planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu):
+            return
+        _hip.xnor_conv2d(planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu)
