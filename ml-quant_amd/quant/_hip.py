@@ -679,6 +679,7 @@ bn_train_lib, bn_train_library_path, BN_TRAIN_ABI_VERSION = _sublib('bn_train')
 conv_chain_lib, conv_chain_library_path, CONV_CHAIN_ABI_VERSION = _sublib('conv_chain')
 weight_train_lib, weight_train_library_path, WEIGHT_TRAIN_ABI_VERSION = _sublib('weight_train')
 conv_xnor_gen_lib, conv_xnor_gen_library_path, CONV_XNOR_GEN_ABI_VERSION = _sublib('conv_xnor_gen')
+stem_gen_lib, stem_gen_library_path, STEM_GEN_ABI_VERSION = _sublib('stem_gen')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1790,6 +1791,52 @@ def xnor_conv2d_gen(planes: torch.Tensor, kx: int, xscales: torch.Tensor, wbits:
         return False
     check(code, what)
     return True
+
+
+# ---- the general small-C front convolution (include/lsq_hip_stem_gen.h)
+def _pair(v) -> Tuple[int, int]:
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def stem_conv_gen_supported(geom: ConvGeom, pool: int) -> bool:
+    """Whether ``stem_conv_gen`` takes the geometry with a ``pool`` x ``pool`` max-pool behind it (lsq_stem_conv_gen_supported,
+    host only): 1..4 input channels, a kernel up to 7 x 7, stride 1 or 2, up to 256 out-channels, pool 1 or 2."""
+    return bool(stem_gen_lib().lsq_stem_conv_gen_supported(ctypes.byref(geom), int(pool)))
+
+
+def stem_conv_gen(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride, padding, relu: bool,
+                  post: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, pool: int = 1) -> torch.Tensor:
+    """``max_pool2d(post(relu(conv2d(x, w, bias, stride, padding))), pool)`` as ONE kernel (lsq_stem_conv_gen), NCHW fp32 in and
+    out, fp32-class accuracy (three bf16 terms per operand).  ``post`` = (scale [O], shift [O]): ``v * scale + shift`` per
+    out-channel behind the ReLU (an eval batch norm folded by the caller); ``pool``: 1 (none) or 2 (2x2 / 2, floor mode).
+    Raises ``LsqHipError`` where the library refuses the geometry (``stem_conv_gen_supported``)."""
+    what = 'lsq_stem_conv_gen'
+    scale, shift = post if post is not None else (None, None)
+    fp32 = {'x': x, 'w': w}
+    fp32.update({k: v for k, v in (('bias', bias), ('post scale', scale), ('post shift', shift)) if v is not None})
+
+    def problem():
+        if x.dim() != 4 or w.dim() != 4 or w.shape[1] != x.shape[1]:
+            return f'x of shape {tuple(x.shape)} and w of shape {tuple(w.shape)} are not a convolution with groups = 1'
+        if (scale is None) != (shift is None):
+            return 'post is a pair (scale, shift)'
+        for name, t in fp32.items():
+            if name not in ('x', 'w') and t.numel() != w.shape[0]:
+                return f'{name} has {t.numel()} elements for {w.shape[0]} out-channels'
+
+    _check_operands(what, fp32, problem=problem)
+    (n, c, h, wd), (o, _, kh, kw) = x.shape, w.shape
+    geom = make_geom(n, c, h, wd, o, kh, kw, _pair(stride), _pair(padding), (1, 1), 1)
+    sl = stem_gen_lib()
+    if not sl.lsq_stem_conv_gen_supported(ctypes.byref(geom), int(pool)):
+        raise LsqHipError(f'{what}: geometry {geom.key()} with pool {pool} is not supported')
+    hc, wc = out_hw(geom)
+    y = torch.empty((n, o, hc // pool, wc // pool), dtype=torch.float32, device=x.device)
+    with _on(x), (_Timed(what, 4 * (x.numel() + w.numel() + y.numel()), 2 * 6 * n * o * hc * wc * c * kh * kw)     # (six MFMA passes)
+                  if _timing is not None else _UNTIMED):
+        check(sl.lsq_stem_conv_gen(x.data_ptr(), w.data_ptr(), ptr(bias), ctypes.byref(geom), int(bool(relu)), ptr(scale),
+                                   ptr(shift), int(pool), y.data_ptr(), stream_ptr(x.device)), what)
+    return y
 
 
 def xnor_impl(mode) -> int:

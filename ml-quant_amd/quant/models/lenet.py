@@ -12,8 +12,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from quant import _hip
 from quant.binary.binary_conv import QuantConv2d
 from quant.binary.binary_linear import QuantLinear
+from quant.models import resnet
 
 
 class QLeNet5(nn.Module):
@@ -44,8 +46,39 @@ class QLeNet5(nn.Module):
                                    fc1_quant.get('clamp'), moving_average_mode, moving_average_momentum)
         self.fc2 = nn.Linear(hidden, output_classes)
 
+    def _bn_conv1_affine(self):
+        """(scale, shift) of the eval-mode ``bn_conv1``: ``1 / sqrt(var + eps)`` and ``-mean / sqrt(var + eps)``, times
+        / plus its weight and bias where it has them; cached against the buffers' versions (as resnet._folded_conv_bn)."""
+        bn = self.bn_conv1
+        tensors = [bn.running_mean, bn.running_var] + ([bn.weight, bn.bias] if bn.affine else [])
+        stamp = tuple((t._version, t.data_ptr()) for t in tensors)
+        hit = self.__dict__.get('_front_affine')
+        if hit is None or hit[0] != stamp:
+            with torch.no_grad():
+                scale = torch.rsqrt(bn.running_var + bn.eps)
+                if bn.affine:
+                    scale = scale * bn.weight
+                shift = -bn.running_mean * scale
+                if bn.affine:
+                    shift = shift + bn.bias
+            hit = self.__dict__['_front_affine'] = (stamp, scale.float().contiguous(), shift.float().contiguous())
+        return hit[1], hit[2]
+
+    def _front(self, x: torch.Tensor) -> torch.Tensor:
+        """``max_pool2d(bn_conv1(relu(conv1(x))), 2, 2)``; with ``resnet.STEM_GENERAL``, in eval mode on a contiguous fp32
+        GPU input, as ONE kernel (lsq_stem_conv_gen: the batch norm is its per-channel affine behind the ReLU)."""
+        bn, conv = self.bn_conv1, self.conv1
+        if (resnet.STEM_GENERAL and not self.training and not bn.training and bn.track_running_stats
+                and bn.running_mean is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                and x.is_contiguous() and not (torch.is_grad_enabled() and x.requires_grad)):
+            geom = resnet._stem_gen_geom(conv, x)
+            if geom is not None and _hip.stem_conv_gen_supported(geom, 2):
+                return _hip.stem_conv_gen(x, conv.weight.detach(), None if conv.bias is None else conv.bias.detach(),
+                                          conv.stride, conv.padding, True, self._bn_conv1_affine(), 2)
+        return F.max_pool2d(bn(F.relu(conv(x))), kernel_size=2, stride=2)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = F.max_pool2d(self.bn_conv1(F.relu(self.conv1(x))), kernel_size=2, stride=2)
+        x = self._front(x)
         # bn -> quantized conv -> relu: one fused call (on the HIP path the batch norm is folded into the
         # quantizer's read and the ReLU into the conv epilogue; elsewhere it is the plain composition)
         x = F.max_pool2d(self.conv2.fused_forward(x, self.bn_conv2, relu=True), kernel_size=2, stride=2)

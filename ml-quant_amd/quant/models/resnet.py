@@ -82,6 +82,28 @@ def _is_resnet_stem(conv: nn.Conv2d, relu: nn.Module, pool: nn.Module, x: torch.
             and two(pool.dilation) == (1, 1) and not pool.ceil_mode)
 
 
+#: set to True to run every OTHER stem geometry lsq_stem_conv_gen takes (the CIFAR stem: 3x3 / 1, no pool) and LeNet's
+#: conv1 + ReLU + batch norm + 2x2 pool (quant/models/lenet.py reads the same switch) as one kernel in eval mode
+STEM_GENERAL = False
+
+
+def _stem_gen_pool(pool: nn.Module) -> Optional[int]:
+    """1 for ``nn.Identity``, 2 for a plain 2x2 / 2 floor-mode ``nn.MaxPool2d`` without padding, else None."""
+    if isinstance(pool, nn.Identity):
+        return 1
+    return 2 if _square_pool(pool) == (2, 2, 0) else None
+
+
+def _stem_gen_geom(conv: nn.Conv2d, x: torch.Tensor):
+    """The geometry of ``conv(x)`` for lsq_stem_conv_gen, or None where ``x`` / ``conv`` are not its operands (contiguous
+    fp32 NCHW, zero padding given as numbers, fp32 weights)."""
+    if not (x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous() and conv.weight.dtype == torch.float32
+            and conv.padding_mode == 'zeros' and not isinstance(conv.padding, str) and x.shape[1] == conv.in_channels):
+        return None
+    return _hip.make_geom(x.shape[0], conv.in_channels, x.shape[2], x.shape[3], conv.out_channels, *conv.kernel_size,
+                          tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups)
+
+
 class _Stem(nn.Sequential):
     """``Sequential(conv1, bn1, relu, maxpool)`` of the reference (same keys).  Eval mode on the GPU: batch
     norm folded into the convolution's weights, MIOpen's convolution in channels-last, and the tail
@@ -105,6 +127,12 @@ class _Stem(nn.Sequential):
                                       'bf16 split (STEM_SPLIT = 3). Outputs of the batches before this warning may hold inf / nan.')
                     split = 3
                 return _hip.stem_conv_pool(x, w, b, split)
+            if STEM_GENERAL and isinstance(relu, nn.ReLU) and not _is_resnet_stem(conv, relu, pool, x):
+                # every other small stem (CIFAR: 3x3 / 1, no pool): conv + bias + ReLU (+ 2x2 pool) in one kernel
+                # (csrc/stem_gen/lsq_stem_gen.hip), NCHW in and out
+                p, geom = _stem_gen_pool(pool), _stem_gen_geom(conv, x)
+                if p is not None and geom is not None and _hip.stem_conv_gen_supported(geom, p):
+                    return _hip.stem_conv_gen(x, w, b, conv.stride, conv.padding, True, None, p)
             # a per-channel bias commutes with max-pooling too: add it on the pooled (4x smaller) tensor.
             # MIOpen's 7x7 stride-2 convolution and the pooling are ~1.3x / ~1.9x faster in channels-last
             # (measured, scripts/stem_bench.py); the bias add writes the NCHW tensor the quantizer reads.
