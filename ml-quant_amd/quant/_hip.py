@@ -680,6 +680,7 @@ conv_chain_lib, conv_chain_library_path, CONV_CHAIN_ABI_VERSION = _sublib('conv_
 weight_train_lib, weight_train_library_path, WEIGHT_TRAIN_ABI_VERSION = _sublib('weight_train')
 conv_xnor_gen_lib, conv_xnor_gen_library_path, CONV_XNOR_GEN_ABI_VERSION = _sublib('conv_xnor_gen')
 stem_gen_lib, stem_gen_library_path, STEM_GEN_ABI_VERSION = _sublib('stem_gen')
+conv_xnor_gen_half_lib, conv_xnor_gen_half_library_path, CONV_XNOR_GEN_HALF_ABI_VERSION = _sublib('conv_xnor_gen_half')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1791,6 +1792,74 @@ def xnor_conv2d_gen(planes: torch.Tensor, kx: int, xscales: torch.Tensor, wbits:
         return False
     check(code, what)
     return True
+
+
+# ---- the general fp4 matrix-core XNOR convolution with a 16-bit epilogue, every plane pass in one launch
+# (include/lsq_hip_conv_xnor_gen_half.h)
+def xnor_conv2d_gen_half_supported(geom: ConvGeom, kx: int, kw_planes: int, dtype: torch.dtype) -> bool:
+    """Whether ``xnor_conv2d_gen_half`` takes the geometry with ``kx`` activation and ``kw_planes`` weight planes and an output of
+    ``dtype`` (lsq_xnor_conv2d_gen_half_supported, host only); where not, the caller keeps ``xnor_conv2d_half``."""
+    return bool(conv_xnor_gen_half_lib().lsq_xnor_conv2d_gen_half_supported(
+        ctypes.byref(geom), int(kx), int(kw_planes), LINEAR_HALF_DTYPES.get(dtype, -1)))
+
+
+def xnor_conv2d_gen_half(planes: torch.Tensor, k: int, xscales: torch.Tensor, wbits: torch.Tensor, wsum: torch.Tensor,
+                         wscales: torch.Tensor, bias: Optional[torch.Tensor], geom: ConvGeom, dtype: torch.dtype,
+                         relu: bool = False, res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
+                         prelu: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """``xnor_conv2d_half`` on the general fp4 matrix-core kernel (lsq_xnor_conv2d_gen_half): the same operands, the same
+    bits, ONE launch whatever the plane counts -- the fp32 running value of the kw * ceil(k / 2) passes stays in registers,
+    there is no workspace.  Returns y [N, O, Ho, Wo] of ``dtype``, or None -- nothing launched -- where the library refuses
+    the call as unsupported (the caller runs ``xnor_conv2d_half``)."""
+    what = 'lsq_xnor_conv2d_gen_half'
+    k = int(k)
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f'{what}: dtype must be torch.bfloat16 or torch.float16, got {dtype}')
+    res = {name: t for name, t in (('res_pre', res_pre), ('res_post', res_post)) if t is not None}
+    wrong = [name for name, t in res.items() if t.dtype != dtype]
+    if wrong:
+        raise TypeError(f'{what}: {", ".join(wrong)} must be {dtype} tensors')
+    fp32 = {'xscales': xscales, 'wscales': wscales}
+    if bias is not None:
+        fp32['bias'] = bias
+    if prelu is not None:
+        fp32['prelu'] = prelu
+    ho, wo = out_hw(geom)
+    shape = (geom.N, geom.O, ho, wo)
+
+    def problem():
+        if k < 1 or wscales.dim() != 2 or wscales.shape[0] < 1 or min(shape) < 1:
+            return f'bad sizes: k={k}, wscales of shape {tuple(wscales.shape)}, output {shape}'
+        if tuple(xscales.shape) != (k, geom.N) or planes.numel() < k * geom.N * geom.groups * (
+                (geom.C // max(geom.groups, 1) + 63) // 64) * (geom.H + 2 * geom.pad_h) * (geom.W + 2 * geom.pad_w):
+            return 'activation planes / scales and (k, geometry) do not match'
+        if wscales.shape[1] != geom.O or wbits.numel() < wscales.shape[0] * _signw_plane_words(geom) \
+                or tuple(wsum.shape) != (wscales.shape[0], geom.O, geom.KH * geom.KW) \
+                or (bias is not None and tuple(bias.shape) != (geom.O,)):
+            return 'weight planes / sums / scales / bias and (kw, geometry) do not match'
+        if prelu is not None and (relu or prelu.numel() not in (1, geom.O)):
+            return f'prelu of {prelu.numel()} slopes on {geom.O} channels' + (' together with relu' if relu else '')
+        for name, t in res.items():
+            if tuple(t.shape) != shape:
+                return f'{name} of shape {tuple(t.shape)} must have the shape of y, {shape}'
+
+    _check_operands(what, fp32, {'planes': planes, 'wbits': wbits}, {'wsum': wsum}, half=list(res.values()), problem=problem)
+    act, slope = _act(relu, None if prelu is None else prelu.detach(), geom.O)
+    dev, kw = planes.device, wscales.shape[0]
+    gl = conv_xnor_gen_half_lib()
+    lib()                                           # (liblsq_hip_conv_xnor_gen_half.so links liblsq_hip.so: the same loaded object)
+    y = torch.empty(shape, dtype=dtype, device=dev)
+    macs = y.numel() * geom.C * geom.KH * geom.KW * k * kw
+    # algorithmic bytes: planes read + 16-bit output written + every 16-bit residual read; no running sum in memory
+    nbytes = geom.N * k * geom.C * geom.H * geom.W // 8 + 2 * y.numel() * (1 + len(res))
+    with _on(y), (_Timed(what, nbytes, macs, f'C{geom.C}_H{geom.H}_s{geom.stride_h}') if _timing is not None else _UNTIMED):
+        code = gl.lsq_xnor_conv2d_gen_half(planes.data_ptr(), k, xscales.data_ptr(), wbits.data_ptr(), wsum.data_ptr(), kw,
+                                           wscales.data_ptr(), ptr(bias), ctypes.byref(geom), act, ptr(slope), ptr(res_pre),
+                                           ptr(res_post), LINEAR_HALF_DTYPES[dtype], y.data_ptr(), stream_ptr(dev))
+    if code == E_UNSUPPORTED:
+        return None
+    check(code, what)
+    return y
 
 
 # ---- the general small-C front convolution (include/lsq_hip_stem_gen.h)

@@ -181,6 +181,14 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: it
     xnor_general = False
 
+    #: with ``xnor_half``: the XNOR convolution of a bf16 / fp16 input takes lsq_xnor_conv2d_gen_half, the general fp4
+    #: matrix-core kernel with a 16-bit epilogue and every plane pass inside one launch (no fp32 running sum in a workspace),
+    #: for the geometries lsq_xnor_conv2d_half serves on the popcount kernel, wherever lsq_xnor_conv2d_gen_half_supported says
+    #: yes: the same operands, the same bits.  The 3x3 layers of the tuned matrix-core kernel and the in-kernel projection are
+    #: not touched.  A switch of its own, independent of ``xnor_general``; False: lsq_xnor_conv2d_half, the default whatever
+    #: the measurement says in the change that adds it
+    xnor_general_half = False
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
             return self._forward_hip(x)
@@ -573,6 +581,12 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                         res_post = sc.tensor()
                     else:
                         res_pre = sc.tensor()
+                if self.xnor_general_half and not _hip.xnor_mfma_eligible(geom, k, n * self.out_channels * ho * wo) \
+                        and _hip.xnor_conv2d_gen_half_supported(geom, k, wscales.shape[0], x.dtype):
+                    y16 = _hip.xnor_conv2d_gen_half(planes, k, scales, wbits, wsum, wscales, bias, geom, x.dtype, relu, res_pre,
+                                                    res_post, prelu)
+                    if y16 is not None:              # (refused: the call below, same bits)
+                        return y16
                 return _hip.xnor_conv2d_half(planes, k, scales, wbits, wsum, wscales, bias, geom, x.dtype, relu, res_pre,
                                              res_post, prelu)
             _hip.xnor_conv2d(planes, k, scales, wbits, wsum, wscales, bias, geom, y)
