@@ -681,6 +681,7 @@ weight_train_lib, weight_train_library_path, WEIGHT_TRAIN_ABI_VERSION = _sublib(
 conv_xnor_gen_lib, conv_xnor_gen_library_path, CONV_XNOR_GEN_ABI_VERSION = _sublib('conv_xnor_gen')
 stem_gen_lib, stem_gen_library_path, STEM_GEN_ABI_VERSION = _sublib('stem_gen')
 conv_xnor_gen_half_lib, conv_xnor_gen_half_library_path, CONV_XNOR_GEN_HALF_ABI_VERSION = _sublib('conv_xnor_gen_half')
+stem_u8_lib, stem_u8_library_path, STEM_U8_ABI_VERSION = _sublib('stem_u8')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1905,6 +1906,64 @@ def stem_conv_gen(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
                   if _timing is not None else _UNTIMED):
         check(sl.lsq_stem_conv_gen(x.data_ptr(), w.data_ptr(), ptr(bias), ctypes.byref(geom), int(bool(relu)), ptr(scale),
                                    ptr(shift), int(pool), y.data_ptr(), stream_ptr(x.device)), what)
+    return y
+
+
+# ---- the front convolution on uint8 pixels (include/lsq_hip_stem_u8.h)
+def stem_conv_u8_supported(geom: ConvGeom, pool: int, layout: int) -> bool:
+    """Whether ``stem_conv_u8`` takes the geometry with max-pool ``pool`` (1: none, 2: 2x2 / 2, 3: 3x3 / 2 / pad 1) behind it
+    and the input in ``layout`` (0: NCHW, 1: channels-last) (lsq_stem_conv_u8_supported, host only)."""
+    return bool(stem_u8_lib().lsq_stem_conv_u8_supported(ctypes.byref(geom), int(pool), int(layout)))
+
+
+def stem_conv_u8(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], in_scale: torch.Tensor, in_shift: torch.Tensor,
+                 stride, padding, relu: bool, post: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                 pool: int = 1) -> torch.Tensor:
+    """``pool(post(relu(conv2d(x * in_scale[c] + in_shift[c], w, bias, stride, padding))))`` as ONE kernel (lsq_stem_conv_u8) on
+    a uint8 ``x`` [N, C, H, W] that is NCHW-contiguous or ``torch.channels_last``-contiguous (read as it lies, decided from the
+    strides); zero padding applies to the normalised image.  fp32 NCHW out, fp32-class accuracy.  ``post`` as in
+    ``stem_conv_gen``; ``pool``: 1 (none), 2 (2x2 / 2, floor mode) or 3 (3x3 / 2, pad 1, floor mode).
+    Raises ``LsqHipError`` where the library refuses the geometry (``stem_conv_u8_supported``)."""
+    what = 'lsq_stem_conv_u8'
+    if x.dtype != torch.uint8:
+        raise TypeError(f'{what}: x must be a torch.uint8 tensor, got {x.dtype}')
+    scale, shift = post if post is not None else (None, None)
+    fp32 = {'w': w, 'in_scale': in_scale, 'in_shift': in_shift}
+    fp32.update({k: v for k, v in (('bias', bias), ('post scale', scale), ('post shift', shift)) if v is not None})
+    tensors = _check_dtypes(what, fp32)
+    if x.dim() != 4 or w.dim() != 4 or w.shape[1] != x.shape[1]:
+        raise ValueError(f'{what}: x of shape {tuple(x.shape)} and w of shape {tuple(w.shape)} are not a convolution with groups = 1')
+    if x.is_contiguous():
+        layout = 0
+    elif x.is_contiguous(memory_format=torch.channels_last):
+        layout = 1
+    else:
+        raise ValueError(f'{what}: x must be contiguous in NCHW or in torch.channels_last')
+
+    def problem():
+        if (scale is None) != (shift is None):
+            return 'post is a pair (scale, shift)'
+        for name, t in fp32.items():
+            want = x.shape[1] if name.startswith('in_') else w.shape[0]
+            if name != 'w' and t.numel() != want:
+                return f'{name} has {t.numel()} elements, not {want}'
+
+    _check_placement(what, tensors, problem)
+    if x.device != w.device:
+        raise ValueError(f'{what}: every operand on the same cuda device')
+    (n, c, h, wd), (o, _, kh, kw) = x.shape, w.shape
+    geom = make_geom(n, c, h, wd, o, kh, kw, _pair(stride), _pair(padding), (1, 1), 1)
+    sl = stem_u8_lib()
+    if not sl.lsq_stem_conv_u8_supported(ctypes.byref(geom), int(pool), layout):
+        raise LsqHipError(f'{what}: geometry {geom.key()} with pool {pool} is not supported')
+    hc, wc = out_hw(geom)
+    shape = ((hc - 1) // 2 + 1, (wc - 1) // 2 + 1) if pool == 3 else (hc // pool, wc // pool)
+    y = torch.empty((n, o) + shape, dtype=torch.float32, device=x.device)
+    with _on(x), (_Timed(what, x.numel() + 4 * (w.numel() + y.numel()), 2 * 3 * n * o * hc * wc * c * kh * kw)     # (three MFMA passes)
+                  if _timing is not None else _UNTIMED):
+        check(sl.lsq_stem_conv_u8(x.data_ptr(), layout, w.data_ptr(), ptr(bias), in_scale.data_ptr(), in_shift.data_ptr(),
+                                  ctypes.byref(geom), int(bool(relu)), ptr(scale), ptr(shift), int(pool), y.data_ptr(),
+                                  stream_ptr(x.device)), what)
     return y
 
 

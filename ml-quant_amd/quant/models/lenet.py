@@ -64,9 +64,30 @@ class QLeNet5(nn.Module):
             hit = self.__dict__['_front_affine'] = (stamp, scale.float().contiguous(), shift.float().contiguous())
         return hit[1], hit[2]
 
+    def set_input_norm(self, mean, std) -> None:
+        """Accept uint8 inputs [N, 1, H, W]: the forward is then the one on ``x.float().div(255).sub(mean).div(std)``.
+        Non-persistent buffers: ``state_dict`` keys stay the reference's."""
+        resnet._set_input_norm(self, mean, std, self.conv1.in_channels)
+
+    def _front_u8(self, x: torch.Tensor) -> torch.Tensor:
+        """``_front`` on a uint8 input; with ``resnet.STEM_U8``, in eval mode on the GPU, ONE kernel (lsq_stem_conv_u8: the
+        normalisation inside, the batch norm as its per-channel affine behind the ReLU, pool 2)."""
+        bn, conv = self.bn_conv1, self.conv1
+        resnet._input_norm(self)
+        if (resnet.STEM_U8 and not self.training and not bn.training and bn.track_running_stats
+                and bn.running_mean is not None and x.is_cuda):
+            gl = resnet._stem_u8_geom(conv, x)
+            if gl is not None and _hip.stem_conv_u8_supported(gl[0], 2, gl[1]):
+                return _hip.stem_conv_u8(x, conv.weight.detach(), None if conv.bias is None else conv.bias.detach(),
+                                         *resnet._u8_affine(self), conv.stride, conv.padding, True, self._bn_conv1_affine(), 2)
+        return self._front(resnet._normalise_u8(self, x))
+
     def _front(self, x: torch.Tensor) -> torch.Tensor:
         """``max_pool2d(bn_conv1(relu(conv1(x))), 2, 2)``; with ``resnet.STEM_GENERAL``, in eval mode on a contiguous fp32
-        GPU input, as ONE kernel (lsq_stem_conv_gen: the batch norm is its per-channel affine behind the ReLU)."""
+        GPU input, as ONE kernel (lsq_stem_conv_gen: the batch norm is its per-channel affine behind the ReLU).  A uint8 input
+        (after ``set_input_norm``) goes through ``_front_u8``."""
+        if x.dtype == torch.uint8:
+            return self._front_u8(x)
         bn, conv = self.bn_conv1, self.conv1
         if (resnet.STEM_GENERAL and not self.training and not bn.training and bn.track_running_stats
                 and bn.running_mean is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4

@@ -104,13 +104,91 @@ def _stem_gen_geom(conv: nn.Conv2d, x: torch.Tensor):
                           tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups)
 
 
+#: set to True to run the stem (and LeNet's front: quant/models/lenet.py reads the same switch) on a uint8 CUDA input in eval
+#: mode as ONE kernel, lsq_stem_conv_u8: the input normalisation of ``set_input_norm`` inside, NCHW or channels-last bytes read
+#: as they lie.  False: a uint8 input is normalised in torch and takes the fp32 routes
+STEM_U8 = False
+
+
+def _set_input_norm(owner: nn.Module, mean, std, channels: int) -> None:
+    """Store the per-channel ``mean`` and ``std`` of a uint8 input (of the pixels scaled to [0, 1], as torchvision's
+    ``Normalize``) on ``owner`` as non-persistent fp32 buffers: they move with the module and stay out of ``state_dict``."""
+    dev = next(owner.parameters()).device
+    vecs = [torch.as_tensor(v, dtype=torch.float32).flatten().clone().to(dev) for v in (mean, std)]
+    if any(v.numel() != channels for v in vecs):
+        raise ValueError(f'set_input_norm: mean and std must have {channels} elements each')
+    owner.register_buffer('input_mean', vecs[0], persistent=False)
+    owner.register_buffer('input_std', vecs[1], persistent=False)
+
+
+def _input_norm(owner: nn.Module):
+    mean, std = owner._buffers.get('input_mean'), owner._buffers.get('input_std')
+    if mean is None or std is None:
+        raise ValueError('a uint8 input needs set_input_norm(mean, std) first')
+    return mean, std
+
+
+def _normalise_u8(owner: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """What a uint8 input means everywhere: the fp32 NCHW batch ``x.float().div(255).sub(mean).div(std)``."""
+    mean, std = _input_norm(owner)
+    return x.float().div(255).sub(mean.float().view(1, -1, 1, 1)).div(std.float().view(1, -1, 1, 1)).contiguous()
+
+
+def _u8_affine(owner: nn.Module):
+    """(in_scale, in_shift) of lsq_stem_conv_u8 = (1 / (255 std), -mean / std), cached against the buffers' versions."""
+    mean, std = _input_norm(owner)
+    stamp = tuple((t._version, t.data_ptr()) for t in (mean, std))
+    hit = owner.__dict__.get('_u8_affine')
+    if hit is None or hit[0] != stamp:
+        with torch.no_grad():
+            hit = owner.__dict__['_u8_affine'] = (stamp, (1.0 / (255.0 * std.float())).contiguous(), (-mean.float() / std.float()).contiguous())
+    return hit[1], hit[2]
+
+
+def _stem_u8_pool(pool: nn.Module) -> Optional[int]:
+    """lsq_stem_conv_u8's pool: 1 for ``nn.Identity``, 2 for a plain 2x2 / 2 floor-mode ``nn.MaxPool2d``, 3 for 3x3 / 2 / pad 1."""
+    if isinstance(pool, nn.Identity):
+        return 1
+    return {(2, 2, 0): 2, (3, 2, 1): 3}.get(_square_pool(pool))
+
+
+def _stem_u8_geom(conv: nn.Conv2d, x: torch.Tensor):
+    """(geometry, layout) of ``conv(x)`` for lsq_stem_conv_u8, or None where ``x`` / ``conv`` are not its operands (uint8 CUDA,
+    NCHW- or channels-last-contiguous, zero padding given as numbers, fp32 weights)."""
+    if not (x.dim() == 4 and x.dtype == torch.uint8 and x.is_cuda and conv.weight.dtype == torch.float32
+            and conv.padding_mode == 'zeros' and not isinstance(conv.padding, str) and x.shape[1] == conv.in_channels):
+        return None
+    layout = 0 if x.is_contiguous() else 1 if x.is_contiguous(memory_format=torch.channels_last) else None
+    if layout is None:
+        return None
+    return _hip.make_geom(x.shape[0], conv.in_channels, x.shape[2], x.shape[3], conv.out_channels, *conv.kernel_size,
+                          tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation), conv.groups), layout
+
+
 class _Stem(nn.Sequential):
     """``Sequential(conv1, bn1, relu, maxpool)`` of the reference (same keys).  Eval mode on the GPU: batch
     norm folded into the convolution's weights, MIOpen's convolution in channels-last, and the tail
     (max-pool, bias, ReLU -- bias and ReLU commute with the max -- and the layout change to the NCHW tensor
-    the quantizer reads) as one kernel, ``lsq_pool_bias_relu_nhwc``."""
+    the quantizer reads) as one kernel, ``lsq_pool_bias_relu_nhwc``.  A uint8 input (after ``set_input_norm``) is the fp32
+    forward on the normalised batch; with ``STEM_U8``, in eval mode on the GPU, one lsq_stem_conv_u8 call."""
+
+    def set_input_norm(self, mean, std) -> None:
+        _set_input_norm(self, mean, std, self[0].in_channels)
+
+    def _forward_u8(self, x: torch.Tensor) -> torch.Tensor:
+        conv, bn, relu, pool = self[0], self[1], self[2], self[3]
+        _input_norm(self)                                      # (the ValueError without set_input_norm, on every route)
+        if STEM_U8 and x.is_cuda and isinstance(relu, nn.ReLU) and _eval_fold_ok(self, bn, x):
+            p, gl = _stem_u8_pool(pool), _stem_u8_geom(conv, x)
+            if p is not None and gl is not None and _hip.stem_conv_u8_supported(gl[0], p, gl[1]):
+                w, b = _folded_conv_bn(self, conv, bn)
+                if w.dtype == torch.float32:
+                    return _hip.stem_conv_u8(x, w, b, *_u8_affine(self), conv.stride, conv.padding, True, None, p)
+        return self.forward(_normalise_u8(self, x))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dtype == torch.uint8:
+            return self._forward_u8(x)
         conv, bn, relu, pool = self[0], self[1], self[2], self[3]
         if _eval_fold_ok(self, bn, x):
             w, b = _folded_conv_bn(self, conv, bn)
@@ -448,6 +526,11 @@ class QResNet(nn.Module):
                                      moving_average_momentum=moving_average_momentum, **layer_config))
             in_planes = out_planes
         return in_planes
+
+    def set_input_norm(self, mean, std) -> None:
+        """Accept uint8 inputs [N, 3, H, W] (NCHW or channels-last): the forward is then the one on
+        ``x.float().div(255).sub(mean).div(std)``.  Non-persistent buffers of the stem: ``state_dict`` keys stay the reference's."""
+        self.blocks[0].set_input_norm(mean, std)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not self.training and x.is_cuda:
