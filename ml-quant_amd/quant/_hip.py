@@ -682,6 +682,7 @@ conv_xnor_gen_lib, conv_xnor_gen_library_path, CONV_XNOR_GEN_ABI_VERSION = _subl
 stem_gen_lib, stem_gen_library_path, STEM_GEN_ABI_VERSION = _sublib('stem_gen')
 conv_xnor_gen_half_lib, conv_xnor_gen_half_library_path, CONV_XNOR_GEN_HALF_ABI_VERSION = _sublib('conv_xnor_gen_half')
 stem_u8_lib, stem_u8_library_path, STEM_U8_ABI_VERSION = _sublib('stem_u8')
+conv_xnor_narrow_lib, conv_xnor_narrow_library_path, CONV_XNOR_NARROW_ABI_VERSION = _sublib('conv_xnor_narrow')
 
 LINEAR_MAX_FEATURES = 1 << 22       # lsq_linear_xnor: F < 2^22 (exact fp32 integers)
 LINEAR_MAX_OUTPUTS = 1 << 21        # lsq_linear_xnor: O < 2^21
@@ -1789,6 +1790,62 @@ def xnor_conv2d_gen(planes: torch.Tensor, kx: int, xscales: torch.Tensor, wbits:
         code = gl.lsq_xnor_conv2d_gen(planes.data_ptr(), kx, xscales.data_ptr(), wbits.data_ptr(), wsum.data_ptr(),
                                       wscales.shape[0], wscales.data_ptr(), ptr(bias), ctypes.byref(geom), act, ptr(slope),
                                       ptr(res_pre), ptr(res_post), y.data_ptr(), stream_ptr(y.device))
+    if code == E_UNSUPPORTED:
+        return False
+    check(code, what)
+    return True
+
+
+# ---- the fp4 matrix-core XNOR convolution for any channel count, with an optional 2 x 2 max-pool
+# (include/lsq_hip_conv_xnor_narrow.h)
+def xnor_conv2d_narrow_supported(geom: ConvGeom, kx: int, kw_planes: int, pool: int = 1) -> bool:
+    """Whether ``xnor_conv2d_narrow`` takes the geometry with ``kx`` activation and ``kw_planes`` weight planes and ``pool``
+    (lsq_xnor_conv2d_narrow_supported, host only); where not, the caller keeps ``xnor_conv2d``."""
+    return bool(conv_xnor_narrow_lib().lsq_xnor_conv2d_narrow_supported(ctypes.byref(geom), int(kx), int(kw_planes), int(pool)))
+
+
+def xnor_conv2d_narrow(planes: torch.Tensor, kx: int, xscales: torch.Tensor, wbits: torch.Tensor, wsum: torch.Tensor,
+                       wscales: torch.Tensor, bias: Optional[torch.Tensor], geom: ConvGeom, y: torch.Tensor,
+                       relu: bool = False, res_pre: Optional[torch.Tensor] = None,
+                       res_post: Optional[torch.Tensor] = None, prelu: Optional[torch.Tensor] = None, pool: int = 1) -> bool:
+    """``xnor_conv2d`` on the fp4 matrix-core kernel for any channel count (lsq_xnor_conv2d_narrow): input channels that are
+    no multiple of 64, out-channels that are no multiple of 32; the same operands, the same bits, every plane pass in one
+    launch.  ``pool=2``: ``y`` is [N, O, Ho // 2, Wo // 2] and receives ``F.max_pool2d(., 2, 2)`` of the result (no
+    residuals).  Returns False -- nothing launched, nothing written -- where the library refuses the call as unsupported
+    (the caller runs ``xnor_conv2d``)."""
+    what = 'lsq_xnor_conv2d_narrow'
+    ho, wo = out_hw(geom)
+    taps = geom.KH * geom.KW
+    full = geom.N * geom.O * ho * wo
+
+    def problem():
+        if pool == 2 and tuple(y.shape) != (geom.N, geom.O, ho // 2, wo // 2):
+            return f'y of shape {tuple(y.shape)} is not the pooled output of the geometry'
+        if pool != 2 and tuple(y.shape) != (geom.N, geom.O, ho, wo):
+            return f'y of shape {tuple(y.shape)} does not match the geometry'
+        if planes.numel() < kx * act_plane_words(geom) or xscales.numel() < kx * geom.N:
+            return f'{kx} activation planes need {kx * act_plane_words(geom)} words and {kx * geom.N} scales'
+        if wscales.dim() != 2 or wscales.shape[1] != geom.O or wsum.numel() != wscales.shape[0] * geom.O * taps:
+            return 'wscales must be [planes, O] and wsum [planes, O, taps]'
+        if wbits.numel() < wscales.shape[0] * lib().lsq_weight_plane_words(ctypes.byref(geom)):
+            return 'wbits is shorter than the weight planes of the geometry'
+        for name, t in (('bias', bias), ('res_pre', res_pre), ('res_post', res_post)):
+            if t is not None and t.numel() != (geom.O if name == 'bias' else full):
+                return f'{name} has {t.numel()} elements'
+
+    fp32 = {'xscales': xscales, 'wscales': wscales, 'y': y}
+    fp32.update({k: v for k, v in (('bias', bias), ('res_pre', res_pre), ('res_post', res_post)) if v is not None})
+    _check_operands(what, fp32, int64={'planes': planes, 'wbits': wbits}, int32={'wsum': wsum}, problem=problem)
+    act, slope = _act(relu, prelu, geom.O)
+    m = geom.C * geom.H * geom.W
+    macs = full * geom.C * taps * kx * wscales.shape[0]
+    nres = (res_pre is not None) + (res_post is not None)
+    gl = conv_xnor_narrow_lib()
+    with _on(y), (_Timed(what, geom.N * kx * m // 8 + 4 * y.numel() * (1 + nres), macs, f'C{geom.C}_H{geom.H}_s{geom.stride_h}',
+                         geom.N * kx * m // 8 + 4 * y.numel()) if _timing is not None else _UNTIMED):
+        code = gl.lsq_xnor_conv2d_narrow(planes.data_ptr(), kx, xscales.data_ptr(), wbits.data_ptr(), wsum.data_ptr(),
+                                         wscales.shape[0], wscales.data_ptr(), ptr(bias), ctypes.byref(geom), act, ptr(slope),
+                                         ptr(res_pre), ptr(res_post), int(pool), y.data_ptr(), stream_ptr(y.device))
     if code == E_UNSUPPORTED:
         return False
     check(code, what)

@@ -188,6 +188,9 @@ SUBLIBS = (
     _entry('stem_u8', '|lsq_stem_conv_u8[a-z0-9_]*', {
         'lsq_stem_conv_u8_supported': (i32, [gp, i32, i32]),
         'lsq_stem_conv_u8': (i32, [vp, i32, vp, vp, vp, vp, gp, i32, vp, vp, i32, vp, vp])}),
+    _entry('conv_xnor_narrow', '|lsq_xnor_conv2d_narrow[a-z0-9_]*', {
+        'lsq_xnor_conv2d_narrow_supported': (i32, [gp, i32, i32, i32]),
+        'lsq_xnor_conv2d_narrow': (i32, [vp, i32, vp, vp, vp, i32, vp, vp, gp, i32, vp, vp, vp, i32, vp, vp])}),
 )
 BY_DIR = {s.dir: s for s in SUBLIBS}
 

@@ -189,6 +189,15 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     #: the measurement says in the change that adds it
     xnor_general_half = False
 
+    #: the plain eval call of the binary-activation branch takes lsq_xnor_conv2d_narrow, the fp4 matrix-core kernel for any
+    #: channel count, for the layers whose input channels are no multiple of 64 or whose out-channels are no multiple of 32
+    #: (LeNet's 20 -> 50 conv2, ResNets of width 16, 48, 80, 96, ...), wherever lsq_xnor_conv2d_narrow_supported says yes: the
+    #: same operands, the same bits, every plane pass in one launch.  ``fused_forward(..., pool=2)`` then pools inside that
+    #: launch.  It is tried in front of ``xnor_general``; the tuned matrix-core kernel's layers and the chained, fixed-scale,
+    #: projection and 16-bit routes are not touched.  A switch of its own; False: lsq_xnor_conv2d (and F.max_pool2d), the
+    #: default whatever the measurement says in the change that adds it
+    xnor_narrow = False
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._wants_hip(x):
             return self._forward_hip(x)
@@ -289,13 +298,21 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     def fused_forward(self, x: torch.Tensor, pre_bn: Optional[nn.BatchNorm2d] = None, relu: bool = False,
                       res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
                       prelu: Optional[torch.Tensor] = None, next_q: Optional[tuple] = None,
-                      res_ready: Optional[torch.cuda.Event] = None) -> torch.Tensor:
+                      res_ready: Optional[torch.cuda.Event] = None, pool: int = 1) -> torch.Tensor:
         """``act(self(pre_bn(x)) + res_pre) + res_post`` -- one residual-block half (quant/models/resnet.py:
         95-100, 182-190); ``act`` = ReLU (``relu=True``), PReLU (``prelu`` = the nn.PReLU weight) or identity.
         One of the two residuals may be a ``ProjectionShortcut`` in place of a tensor.
         On the HIP path the eval-mode batch norm is folded into the quantizer's read and the non-linearity /
         shortcut additions into the convolution's epilogue, so none of them is a separate pass over HBM;
-        elsewhere it is the plain composition of the modules."""
+        elsewhere it is the plain composition of the modules.
+        ``pool=2``: ``F.max_pool2d(., 2, 2)`` of that -- with ``xnor_narrow``, inside lsq_xnor_conv2d_narrow's launch where
+        ``_pools_in_kernel`` says so, else as the torch call behind the ``pool=1`` result."""
+        if pool != 1:
+            if pool != 2:
+                raise ValueError(f'pool must be 1 or 2, not {pool}')
+            if res_pre is None and res_post is None and next_q is None and self._pools_in_kernel(x, pre_bn):
+                return self._forward_hip(x, pre_bn, relu, None, None, prelu, None, res_ready, pool=2)
+            return F.max_pool2d(self.fused_forward(x, pre_bn, relu, res_pre, res_post, prelu, next_q, res_ready), 2, 2)
         xin = None
         # act_half_bn_fold: the batch norm of a 16-bit input goes into the quantizer's read (lsq_act_quant_bn_half) instead of
         # a torch pass of its own -- here and in the composition below
@@ -355,6 +372,28 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
         if prelu is not None:
             y = F.prelu(y, prelu)
         return y if res_post is None else y + res_post
+
+    def _narrow_takes(self, _hip, geom, k: int, kw_planes: int, outputs: int, pool: int = 1) -> bool:
+        """Whether the plain call of this geometry goes to lsq_xnor_conv2d_narrow (``xnor_narrow``): a layer outside the tuned
+        matrix-core kernel whose channel counts keep it off lsq_xnor_conv2d_gen too, and that the library accepts."""
+        return (self.xnor_narrow and not _hip.xnor_mfma_eligible(geom, k, outputs) and (geom.C % 64 != 0 or geom.O % 32 != 0)
+                and _hip.xnor_conv2d_narrow_supported(geom, k, kw_planes, pool))
+
+    def _pools_in_kernel(self, x: torch.Tensor, pre_bn: Optional[nn.BatchNorm2d]) -> bool:
+        """Whether ``fused_forward(..., pool=2)`` without residuals or ``next_q`` ends in ONE lsq_xnor_conv2d_narrow with
+        pool 2: ``xnor_narrow``, the fp32 HIP route with binary activations and no planes handed over by a producer, and a
+        geometry the narrow call accepts with the pool."""
+        if not (self.xnor_narrow and x.is_cuda and x.dtype == torch.float32 and self.x_quant != 'fp' and self._wants_hip(x)
+                and (pre_bn is None or (not pre_bn.training and pre_bn.track_running_stats))):
+            return False
+        from quant import _hip
+        from quant.binary import chain
+        if chain.pending(x) is not None:
+            return False
+        geom = self._geom_of(x, _hip)
+        ho, wo = _hip.out_hw(geom)
+        return self._narrow_takes(_hip, geom, self.x_approximate.n_planes, self.w_approximate.n_planes,
+                                  x.shape[0] * self.out_channels * ho * wo, 2)
 
     def _folds_half_bn(self, x: torch.Tensor, bn: nn.BatchNorm2d) -> bool:
         """Whether ``fused_forward`` folds ``bn`` into the 16-bit quantizer's read (``act_half_bn_fold``): a bf16 / fp16 CUDA
@@ -517,7 +556,9 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
     def _forward_hip(self, x: torch.Tensor, pre_bn: Optional[nn.BatchNorm2d] = None, relu: bool = False,
                      res_pre: Optional[torch.Tensor] = None, res_post: Optional[torch.Tensor] = None,
                      prelu: Optional[torch.Tensor] = None, next_q: Optional[tuple] = None,
-                     res_ready: Optional[torch.cuda.Event] = None) -> torch.Tensor:
+                     res_ready: Optional[torch.cuda.Event] = None, pool: int = 1) -> torch.Tensor:
+        # pool = 2 (from fused_forward, where ``_pools_in_kernel`` holds: fp32, binary activations, no residuals, no next_q,
+        # nothing handed over): y is the pooled tensor, and the call ends in ``_xnor_plain`` with the pool
         from quant import _hip
         from quant.binary import chain
         # a ProjectionShortcut in a residual slot: only the plain two-plane XNOR call at the end computes it itself (at most
@@ -547,7 +588,7 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
             # Tensor.clamp would round it into their type; the kernel rounds its fp32 result once into the input's type
             return _hip.signw_conv2d_half(x.contiguous(), self._alpha_in(x.dtype), wbits, wscales, bias, geom)
         half_out = self.xnor_half and x.dtype != torch.float32 and self.x_quant != 'fp'      # (lsq_xnor_conv2d_half allocates its y)
-        y = None if half_out else torch.empty((n, self.out_channels, ho, wo), dtype=torch.float32, device=x.device)
+        y = None if half_out else torch.empty((n, self.out_channels, ho // pool, wo // pool), dtype=torch.float32, device=x.device)
         def join():                      # residual operands from a side stream: in front of the convolution, behind the quantizer
             if res_ready is not None:
                 torch.cuda.current_stream(x.device).wait_event(res_ready)
@@ -606,7 +647,7 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                     and handed.stamp is not None and handed.stamp == xq.eval_scales_stamp()):
                 fixed_in = handed
             handed = None                              # (never the row sums of the ls-1 chain below)
-        if self.x_quant == 'ls-1' and chain.ENABLED and fixed_in is None:
+        if self.x_quant == 'ls-1' and chain.ENABLED and fixed_in is None and pool == 1:
             # chained 1-bit layers: take the planes and row sums the producer's epilogue left for THIS call, and / or leave
             # the consumer's in this call's epilogue
             stream = _hip.stream_ptr(x.device)
@@ -654,13 +695,26 @@ class QuantConv2d(HipQuantModule, nn.Conv2d):
                 res_post = sc.tensor()
             else:
                 res_pre = sc.tensor()
-        self._xnor_plain(_hip, planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu)
+        self._xnor_plain(_hip, planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu, pool)
         self.last_act_scales = scales
         return y
 
-    def _xnor_plain(self, _hip, planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu):
-        """The plain eval call: lsq_xnor_conv2d, or with ``xnor_general`` lsq_xnor_conv2d_gen first for the geometries the
-        popcount kernel would serve (refused: lsq_xnor_conv2d, same bits)."""
+    def _xnor_plain(self, _hip, planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu,
+                    pool: int = 1):
+        """The plain eval call: lsq_xnor_conv2d; with ``xnor_narrow`` lsq_xnor_conv2d_narrow first for the layers whose channel
+        counts keep them off the matrix cores, then with ``xnor_general`` lsq_xnor_conv2d_gen for the other geometries the
+        popcount kernel would serve (refused: lsq_xnor_conv2d, same bits).  ``pool=2``: ``y`` is the pooled tensor and only the
+        narrow call can fill it (``_pools_in_kernel`` has asked it)."""
+        outputs = y.numel()
+        if pool != 1:                    # (y is the pooled tensor)
+            ho, wo = _hip.out_hw(geom)
+            outputs = y.shape[0] * y.shape[1] * ho * wo
+        if self.xnor_narrow and self._narrow_takes(_hip, geom, k, wscales.shape[0], outputs, pool) \
+                and _hip.xnor_conv2d_narrow(planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu,
+                                            pool):
+            return
+        if pool != 1:
+            raise RuntimeError('lsq_xnor_conv2d_narrow refused a pooled call it had declared supported')
         if self.xnor_general and not _hip.xnor_mfma_eligible(geom, k, y.numel()) \
                 and _hip.xnor_conv2d_gen_supported(geom, k, wscales.shape[0]) \
                 and _hip.xnor_conv2d_gen(planes, k, scales, wbits, wsum, wscales, bias, geom, y, relu, res_pre, res_post, prelu):

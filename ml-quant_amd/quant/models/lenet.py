@@ -102,6 +102,7 @@ class QLeNet5(nn.Module):
         x = self._front(x)
         # bn -> quantized conv -> relu: one fused call (on the HIP path the batch norm is folded into the
         # quantizer's read and the ReLU into the conv epilogue; elsewhere it is the plain composition)
-        x = F.max_pool2d(self.conv2.fused_forward(x, self.bn_conv2, relu=True), kernel_size=2, stride=2)
+        # (the 2 x 2 pool is asked of the same call: with ``QuantConv2d.xnor_narrow`` it runs inside the convolution's launch)
+        x = self.conv2.fused_forward(x, self.bn_conv2, relu=True, pool=2)
         x = F.relu(self.fc1(x.reshape(-1, self.conv2_filters * 4 * 4)))
         return F.log_softmax(self.fc2(x), dim=1)
